@@ -2,7 +2,15 @@
 """Benchmark of the MI355X bilateral-filter family (BASELINE.json metric:
 "Mpixels/sec bilateral r=7 on 4K RGB; % HBM roofline; 1/2/4/8-GPU scaling").
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4|c5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4|c5] [--full] [--dump-outputs DIR]
+
+A plain run sets up, settles the clocks, picks the form (the trial below), warms up, times
+the K steps and prints the line: metric, value, ms_per_step and what describes the run.
+--full adds what takes runs of its own: the roofline object and the per-kernel durations
+(event-stamped steps after the timed region), the N > 1 step's parts and frame latency, the
+weak-scaling figure and the CPU baseline. --dump-outputs DIR writes the output frame of the
+last timed step as DIR/dst.npy (float32; N > 1: dst_rank<r>.npy; a seeded sample of a frame
+too large for the file), the same from run to run for the same arguments.
 
 One step = one filter application over each rank's row slab of a frame that is
 row-sharded across the N GPUs (one process per GPU, torch.distributed over
@@ -15,8 +23,8 @@ communicators, one per stream), then filter their own rows.
 
   c2 (default) bilateral r=7 (ksize 15, sigma_space 10, sigma_color 30) on the
      3840x2160 RGB8 frame, its rows split over the N ranks (strong scaling: BASELINE
-     config 2 at every N); the line also reports the weak-scaling figure (a 2160-row
-     slab per rank of an (N*2160)x3840 frame) under "weak".
+     config 2 at every N); with --full the line also reports the weak-scaling figure (a
+     2160-row slab per rank of an (N*2160)x3840 frame) under "weak".
   c3 adaptive bilateral r=7, same geometry (BASELINE config 3).
   c4 bilateral texture filter k=5, nitr=5 on 3840x2160 per rank (BASELINE config
      4); N>1 row-shards an (N*2160)x3840 frame with one 45-row halo exchange per
@@ -27,7 +35,7 @@ communicators, one per stream), then filter their own rows.
 
 Inputs are synthetic (test/random_array-style uniform u8), resident in HBM before
 timing; 12 distinct input/output slabs rotate so the working set exceeds the
-256 MB Infinity Cache. Rank 0 prints ONE JSON line. The roofline object is for
+256 MB Infinity Cache. Rank 0 prints ONE JSON line. The roofline object (--full) is for
 the dominant kernel, timed with HIP events on the stream it runs on, beside the
 committed single-stream rocprofv3 launch sample of the same instantiation; the CPU
 baseline (rank 0, N=1) is the oracle's include/cpp restatement on the host cores.
@@ -35,7 +43,7 @@ baseline (rank 0, N=1) is the oracle's include/cpp restatement on the host cores
 Before the timed steps a trial picks how frames overlap, with the same grid at every N:
 S streams x B frames per shared launch (N = 1) or per RCCL group (N > 1, where the trial
 also crosses the interior/edge split and the CUs a shared launch leaves free); the line
-reports `frames_in_flight` (S x B) and `frame_latency_ms`. An N > 1 line carries `rccl`
+reports `frames_in_flight` (S x B) and, with --full, `frame_latency_ms`. An N > 1 line carries `rccl`
 (what RCCL reports about every rank's communicators and devices) and `valid`.
 """
 from __future__ import annotations
@@ -59,6 +67,7 @@ LAUNCH_TIMING = ("vip_kernel_timing: hipExtLaunchKernel events stamped with each
                  "max(4, K/4) frames back to back on one stream after the timed region")
 VALU_CYCLES_PER_INSTR = 2    # a wave64 VALU instruction issues over 2 cycles (MI355X_MICROARCH.md)
 NBUF = 12
+DUMP_MAX_ELEMS = 12 * 2 ** 20  # --dump-outputs: float32 values over all ranks (48 MiB)
 
 
 LAUNCH_TIMEOUT_S = 1500.0  # whole N-rank run, launcher included
@@ -190,7 +199,7 @@ def native_forms(stream_counts, texture: bool, batches=None) -> list:
 
 def multi_gpu_wall_estimate_s(config: str, n: int, step_ms: float, steps=None, warmup: int = 20,
                               settle_s: float = 6.0) -> float:
-    """Worst-case device wall time of one `bench.py --gpus n` line (n > 1, native exchange,
+    """Worst-case device wall time of one `bench.py --gpus n --full` line (n > 1, native exchange,
     no --streams / --batch): the settle, every trial form (NBUF untimed + 48 timed steps, plus
     ~5 ms of syncs and barriers each), the warm-up, the K timed steps and the K/4 evented
     steps -- twice for the strong-scaling configs, whose line also measures the weak figure
@@ -275,7 +284,19 @@ def parse():
     # (the driver's rocm-smi) then sees the device busy in at least one sample
     p.add_argument("--settle-s", type=float, default=6.0)
     p.add_argument("--config", default="c2", choices=sorted(CONFIGS))
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    # a plain run does what the headline figure needs: set-up, settle, the trial that picks the
+    # form, warm-up, the K timed steps, the line. --full adds everything that takes runs of its
+    # own: the event-stamped steps after the timed region (roofline, kernel durations, the
+    # N > 1 step's parts and latency), the weak-scaling figure of a strong N > 1 line and the
+    # CPU baseline
+    p.add_argument("--full", action="store_true",
+                   help="also measure the roofline / per-kernel durations, the weak-scaling figure and the CPU baseline")
+    # after the timed steps: the output frame of the last timed step (every rank's own rows) as
+    # DIR/dst.npy (N > 1: DIR/dst_rank<r>.npy), float32; a frame above DUMP_MAX_ELEMS values is
+    # cut to a fixed seeded sample of them. The inputs are seeded and every phase starts on
+    # buffer 0, so equal arguments give equal files from run to run and from build to build
+    p.add_argument("--dump-outputs", default=None, metavar="DIR")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     # rehearsal only: gloo + every rank on cuda:0 runs the N>1 code path on a 1-GPU box
     p.add_argument("--backend", default="nccl", choices=["nccl", "gloo"])
     p.add_argument("--same-device", action="store_true")
@@ -628,6 +649,24 @@ def sample_table(args) -> None:
     for name, cpp, hip in rows:
         print(f"{name + ' [cpp]':40s} : {measure(cpp):10.6f} [msec]")
         print(f"{name + ' [hip]':40s} : {measure(hip):10.6f} [msec]")
+
+
+def dump_outputs(dirname: str, dst, rank: int, world: int) -> dict:
+    """--dump-outputs: this rank's output frame of the last timed step (the u8 rows a caller's
+    dst buffer holds after the call) as float32 in DIR/dst.npy (N > 1: DIR/dst_rank<r>.npy).
+    A frame of more than DUMP_MAX_ELEMS / N values is cut to that many values at positions
+    drawn once from a fixed seed (sorted, with repeats), the same for every run of the same
+    geometry. Returns what the line says about the file."""
+    os.makedirs(dirname, exist_ok=True)
+    a = dst.cpu().numpy().reshape(-1)
+    cap = DUMP_MAX_ELEMS // max(1, world)
+    sampled = a.size > cap
+    if sampled:
+        a = a[np.sort(np.random.default_rng(20240 + rank).integers(0, a.size, size=cap))]
+    name = "dst.npy" if world == 1 else f"dst_rank{rank}.npy"
+    np.save(os.path.join(dirname, name), a.astype(np.float32))
+    return dict(file=name, dtype="float32", values=int(a.size), shape=list(dst.shape),
+                sample=f"{cap} seeded positions of the flattened frame" if sampled else None)
 
 
 def init_distributed(args, rank, dev):
@@ -991,7 +1030,8 @@ def measure(args, cfg, frame_h, torch, dev, rank, world, streams, state, s_forms
         # as many steps as fill about a quarter of the timed region (a multiple of every B)
         # after one untimed pass over the buffers; keep the fastest.
         trial = {}
-        n_trial = NBUF * max(4, args.steps // 48)
+        # (of the config's default timed region at most: a longer --steps run buys no longer trial)
+        n_trial = NBUF * max(4, min(args.steps, DEFAULT_STEPS[args.config]) // 48)
         s_first = sorted(s_forms, key=lambda n: n != args.streams)  # the config's stream count first
         forms = [f for f in cfg.get("single_gpu_forms", single_gpu_forms(s_first, batches))
                  if f[0] <= len(streams) and (batches is None or f[1] in batches)] or single_gpu_forms(s_first, batches)
@@ -1064,7 +1104,13 @@ def measure(args, cfg, frame_h, torch, dev, rank, world, streams, state, s_forms
     parts = None
     B = hb["B"]
     res["frames_in_flight"] = S_run * B
-    if multi:
+    if args.dump_outputs:  # the last timed step's output frame, before anything else writes a buffer
+        res["last_dst"] = dsts[(t_first + args.steps - 1) % NBUF].clone()
+    if not args.full:
+        # a plain run ends with the timed region: its own time per step (N = 1: between the
+        # events around it), no event-stamped steps after it
+        kernel_ms = (elapsed * 1e3 if multi else ev0.elapsed_time(ev1)) / args.steps
+    elif multi:
         for i in range(max(4, args.steps // 4)):
             step(after + i, sample=True)
         torch.cuda.synchronize(dev)
@@ -1152,12 +1198,14 @@ def measure(args, cfg, frame_h, torch, dev, rank, world, streams, state, s_forms
     # one frame's latency: the whole launch that carries it on an idle stream (N = 1) or
     # its RCCL group's exchange and launches (N > 1); the reference's public call blocks for
     # one frame (sample/benchmark/main.cpp:20-33 times one call per frame)
-    if not multi:
+    if not args.full:
+        pass  # no one-frame launch was timed
+    elif not multi:
         res["frame_latency_ms"] = launch_ms * B
     elif parts:
         res["frame_latency_ms"] = parts.get("group_latency_ms", parts.get("run_ms", kernel_ms))
     fused = cfg["kind"] == "texture" and world == 1 and not args.loopback and args.texture_mode == "fused"
-    if cfg["kind"] == "texture" and world == 1 and not args.loopback and not fused:
+    if args.full and cfg["kind"] == "texture" and world == 1 and not args.loopback and not fused:
         # per-stage kernel durations (vip_kernel_timing), per launch
         kd = res["kernel_durations"]
         g_ = [v["mean_ms"] for n, v in kd.items() if n.startswith("void vip::texture_guide_fused_kernel")]
@@ -1269,8 +1317,9 @@ def main():
         s_forms = list(TRIAL_STREAMS)
         streams += [torch.cuda.Stream(dev) for _ in range(max(s_forms) - len(streams))]
     m = measure(args, cfg, frame_h, torch, dev, rank, world, streams, state, s_forms)
+    dump_dir, args.dump_outputs = args.dump_outputs, None  # the headline measurement's frame only
     weak = None
-    if world > 1 and args.scaling == "strong" and per_rank and not args.no_weak:
+    if args.full and world > 1 and args.scaling == "strong" and per_rank and not args.no_weak:
         # the weak-scaling figure beside it: a full 2160-row slab per rank of an
         # (N*2160)x3840 frame
         wm = measure(args, cfg, per_rank * world, torch, dev, rank, world, streams, state, s_forms)
@@ -1288,7 +1337,9 @@ def main():
     ms_per_step = elapsed / args.steps * 1e3
     value = total_px / (elapsed / args.steps) / 1e6
 
-    if m["fused"]:
+    if not args.full:
+        roof = None  # the roofline rests on launch durations that only --full measures
+    elif m["fused"]:
         roof = texture_fused_roofline(cfg, px_per_rank, launch_ms, m["kernels"])
     elif cfg["kind"] == "texture":
         roof = texture_roofline(args.config, cfg, px_per_rank, launch_ms, m["stage_ms"], m["kernels"])
@@ -1358,12 +1409,13 @@ def main():
                    **({"texture_mode": args.texture_mode} if cfg["kind"] == "texture" and world == 1 else {}),
                    **({"backend": state.get("backend"), "exchange": m["exchange"]} if state["multi"] else {}),
                    **({"exchange_fallback": m["exchange_fallback"]} if m.get("exchange_fallback") else {})},
-        "roofline": roof,
+        "full": args.full,
+        **({"roofline": roof} if args.full else {}),
         "kernels": m["kernels"],
         # per step, max over ranks: one frame on one stream (N>1: with its exchange),
         # event-timed in max(4, K/4) steps after the timed region; the roofline's launch
-        # durations come from it
-        "kernel_ms": round(launch_ms, 4),
+        # durations come from it (--full)
+        **({"kernel_ms": round(launch_ms, 4)} if args.full else {}),
         # frames in flight on S streams (step i on stream i % S); at N=1 and S>1 the
         # timed region's device time per frame, all streams together
         "streams": m.get("streams", S),
@@ -1419,7 +1471,9 @@ def main():
         out["rehearsal"] = (f"one GPU: the middle rank's slab of a {args.loopback}-way row split, its two neighbours "
                             f"the rank itself over a one-rank RCCL communicator (vip_shard_create_loopback); value "
                             f"counts this slab only -- not a scaling number")
-    if rank == 0 and not sharded and not args.no_cpu_baseline:
+    if dump_dir:
+        out["outputs"] = dump_outputs(dump_dir, m["last_dst"], rank, world)
+    if args.full and rank == 0 and not sharded and not args.no_cpu_baseline:
         try:
             out["cpu_baseline"] = cpu_baseline(cfg)
         except Exception as e:  # the baseline is reported, never required

@@ -57,14 +57,14 @@ for step in "$@"; do
       rc=$?; tail -2 $O/${TAG}_smoke.log; [ $rc -eq 0 ] || fail "$step" $rc $O/${TAG}_smoke.log ;;
     bench)
       cfg=${A[0]}; out=$O/${TAG}_${cfg}_bench.json
-      timeout -k 10 400 python bench.py --config $cfg "${A[@]:1}" > $out 2> $O/${TAG}_${cfg}_bench.err
+      timeout -k 10 400 python bench.py --full --config $cfg "${A[@]:1}" > $out 2> $O/${TAG}_${cfg}_bench.err
       rc=$?; cut -c1-600 $out; [ $rc -eq 0 ] || fail "$step" $rc $O/${TAG}_${cfg}_bench.err ;;
     stats)
       cfg=${A[0]}; steps=20; [ $cfg = c5 ] && steps=5; d=$O/prof_${TAG}_$cfg
       # one stream and a 1 s settle: the summary's average is then a launch duration (with two
       # streams the launches overlap and the settle's queued frames dominate the count)
       timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $d -o run --output-format csv -- \
-        python bench.py --config $cfg --steps $steps --warmup 3 --no-cpu-baseline --streams 1 --batch 1 \
+        python bench.py --full --config $cfg --steps $steps --warmup 3 --no-cpu-baseline --streams 1 --batch 1 \
         --settle-s 1 "${A[@]:1}" > $d.log 2>&1
       rc=$?; [ $rc -eq 0 ] || fail "$step" $rc $d.log
       cp $d/run_kernel_stats.csv $O/${TAG}_${cfg}_kernel_stats.csv
@@ -77,7 +77,7 @@ for step in "$@"; do
       cfg=${A[0]}; steps=1200; [ $cfg = c5 ] && steps=240; [ $cfg = c4 ] && steps=300; [ $cfg = c2 ] && steps=408
       [ $cfg = c3 ] && steps=408; d=$O/iso_${TAG}_$cfg
       timeout -k 10 500 rocprofv3 --kernel-trace -d $d -o run --output-format csv -- \
-        python bench.py --config $cfg --streams 1 --batch 1 --steps $steps --warmup 12 --no-cpu-baseline \
+        python bench.py --full --config $cfg --streams 1 --batch 1 --steps $steps --warmup 12 --no-cpu-baseline \
         "${A[@]:1}" > $d.log 2>&1
       rc=$?; [ $rc -eq 0 ] || fail "$step" $rc $d.log
       fpl=1; for ((j = 1; j < ${#A[@]}; ++j)); do [ "${A[$j]}" = --batch ] && fpl=${A[$((j + 1))]}; done
@@ -89,7 +89,7 @@ for step in "$@"; do
       for set in "${PMC_SETS[@]}"; do
         i=$((i+1))
         timeout -s KILL 240 rocprofv3 --kernel-trace --pmc $set -d $d/p$i -o run --output-format csv -- \
-          python bench.py --config $cfg --streams 1 --batch 1 --steps 12 --warmup 12 --settle-s 0.3 --no-cpu-baseline \
+          python bench.py --full --config $cfg --streams 1 --batch 1 --steps 12 --warmup 12 --settle-s 0.3 --no-cpu-baseline \
           "${A[@]:1}" > $d/p$i.log 2>&1
         rc=$?; echo "pmc pass $i rc=$rc"; [ $rc -eq 0 ] || fail "$step pass $i" $rc $d/p$i.log
       done
@@ -98,12 +98,12 @@ for step in "$@"; do
       rm -rf $d/p*/ ;;  # the per-dispatch counter tables stay on the box
     rehearse)
       cfg=${A[0]}; n=${A[1]}; sfx=$(printf '%s' "${A[*]:2}" | tr -c 'a-zA-Z0-9' '_'); out=$O/${TAG}_${cfg}_loopback$n$sfx.json
-      timeout -k 10 400 python bench.py --config $cfg --rehearse-native --loopback $n --steps 400 "${A[@]:2}" \
+      timeout -k 10 400 python bench.py --full --config $cfg --rehearse-native --loopback $n --steps 400 "${A[@]:2}" \
         > $out 2> ${out%.json}.err
       rc=$?; cut -c1-1500 $out; [ $rc -eq 0 ] || fail "$step" $rc ${out%.json}.err ;;
     gloo)
       cfg=${A[0]}; n=${A[1]}; out=$O/${TAG}_${cfg}_gloo$n.json
-      timeout -k 10 500 python bench.py --gpus $n --same-device --backend gloo --config $cfg --steps 8 \
+      timeout -k 10 500 python bench.py --full --gpus $n --same-device --backend gloo --config $cfg --steps 8 \
         --warmup 1 "${A[@]:2}" > $out 2> $O/${TAG}_${cfg}_gloo$n.err
       rc=$?; cut -c1-800 $out; [ $rc -eq 0 ] || fail "$step" $rc $O/${TAG}_${cfg}_gloo$n.err ;;
     py)

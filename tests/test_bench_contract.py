@@ -456,3 +456,35 @@ def test_pmc_summary_records_frames_per_launch(tmp_path):
     assert "frames_per_launch" not in k["void vip::bilateral_kernel<5, 16>"]
     e = k["void vip::bilateral_frames_kernel<5, 16>"]
     assert e["traffic_bytes"] == (2 * 30 + 60) * 1024
+
+
+def test_plain_run_options(monkeypatch):
+    """A plain run measures the headline only: --full (off by default) turns on what takes
+    runs of its own, --dump-outputs names the directory of the last step's output frame."""
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "d"
+
+
+def test_dump_outputs_is_float32_bounded_and_repeatable(tmp_path, monkeypatch):
+    """bench.dump_outputs: a small frame whole, a large one as the same seeded sample every
+    time, float32, N > 1 one file per rank, never above DUMP_MAX_ELEMS values over the ranks."""
+    import numpy as np
+    import torch
+    assert bench.DUMP_MAX_ELEMS * 4 <= 64e6
+    frame = (torch.arange(7 * 5 * 3, dtype=torch.int64) % 251).to(torch.uint8).reshape(7, 5, 3)
+    info = bench.dump_outputs(str(tmp_path / "a"), frame, 0, 1)
+    got = np.load(tmp_path / "a" / "dst.npy")
+    assert info["file"] == "dst.npy" and info["sample"] is None and got.dtype == np.float32
+    np.testing.assert_array_equal(got, frame.numpy().reshape(-1).astype(np.float32))
+    monkeypatch.setattr(bench, "DUMP_MAX_ELEMS", 40)
+    for d in ("b", "c"):
+        for rank in (0, 1):
+            bench.dump_outputs(str(tmp_path / d), frame, rank, 2)
+    for rank in (0, 1):
+        b, c = (np.load(tmp_path / d / f"dst_rank{rank}.npy") for d in ("b", "c"))
+        assert b.dtype == np.float32 and b.size == 20 and np.array_equal(b, c)
+        assert set(b.tolist()) <= set(frame.numpy().reshape(-1).astype(np.float32).tolist())

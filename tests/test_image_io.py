@@ -6,7 +6,7 @@ read_image must give what cv::imread(path, IMREAD_COLOR) gives the reference's s
 dropped, gray replicated, palette expanded, 16-bit reduced to the high byte, 1/2/4-bit
 gray scaled to 0..255. The PNG inputs here come from an independent encoder written in
 this file (every colour type and bit depth, all five row filters, Adam7), from PIL, and
--- in this container only -- the reference's own sample images, whose decode must equal
+the reference's own sample image (tests/golden/lenna.png), whose decode must equal
 tests/golden/lenna_bgr.npz (the fixture every lenna test uses).
 """
 import os
@@ -19,7 +19,7 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EXE = os.path.join(ROOT, "samples", "vip_filter")
-REF_IMAGES = "/root/reference/sample_image"
+REF_LENNA = os.path.join(ROOT, "tests", "golden", "lenna.png")  # the reference's sample_image/lenna.png
 
 ADAM7 = [(0, 0, 8, 8), (4, 0, 8, 8), (0, 4, 4, 8), (2, 0, 4, 4), (0, 2, 2, 4), (1, 0, 2, 2), (0, 1, 1, 2)]
 
@@ -208,7 +208,6 @@ def test_corrupt_inputs_are_rejected(tmp_path):
     assert r.returncode == 1
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_IMAGES), reason="reference sample images only exist in the build container")
 def test_reference_lenna_decodes_to_fixture(tmp_path, lenna):
-    got = decode(tmp_path, open(os.path.join(REF_IMAGES, "lenna.png"), "rb").read())
+    got = decode(tmp_path, open(REF_LENNA, "rb").read())
     np.testing.assert_array_equal(got, lenna)
