@@ -2,7 +2,7 @@
 # Build a libvip variant in which ONE CMake object target is recompiled with extra flags and
 # every other object comes from the in-place CMake build (__graft_entry__.build()):
 #   build_object_variant.sh <name> <target> <source> <flags...>  -> variants/<name>.so
-# e.g. build_object_variant.sh jbf_ablcvt vip_bil_joint_fma vip_bilateral.hip -DVIP_BIL_JOINT -DVIP_BIL_FMA -DVIP_ABL_CVT
+# e.g. build_object_variant.sh bil_stamps vip_bil_plain_fma vip_bilateral.hip -DVIP_BIL_FMA -DVIP_STAMPS
 # (the target's own -D definitions must be repeated: CMakeLists.txt vip_variant lines)
 set -e
 name=$1; target=$2; src=$3; shift 3

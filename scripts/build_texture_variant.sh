@@ -1,6 +1,7 @@
 #!/bin/bash
 # Build a libvip variant with an alternative texture build into /root/repo/variants/<name>.so
-# usage: build_texture_variant.sh <name> <extra hipcc flags...>   (e.g. -DVIP_GF_TH=32)
+# usage: build_texture_variant.sh <name> <extra hipcc flags...>   (e.g. -DVIP_GF_STAMPS, -DVIP_GF_ONLY_R2)
+# The sources carry no experiment knobs: a variant is an edited vip_texture.hip, or one of those two builds.
 set -e
 name=$1; shift
 cd "$(dirname "$0")/../various_image_processings_amd/csrc"

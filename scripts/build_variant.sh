@@ -1,6 +1,7 @@
 #!/bin/bash
 # Build an experimental R=7 plain-FMA bilateral library variant into /root/repo/variants/<name>.so
-# usage: build_variant.sh <name> <extra hipcc flags...>
+# usage: build_variant.sh <name> <extra hipcc flags...>   (e.g. -DVIP_STAMPS for stamp_bench.py; the sources
+# carry no experiment knobs, so any other variant is built from edited sources)
 set -e
 name=$1; shift
 cd "$(dirname "$0")/../various_image_processings_amd/csrc"

@@ -13,14 +13,12 @@
 // packed R|B lanes when (2R+1)^2*255 < 2^16), then a horizontal sliding window.
 #include "vip_stencil.hpp"
 
-#ifndef VIP_ADA_P
-#define VIP_ADA_P 4
-#endif
-#ifndef VIP_ADA_UNROLL  // straight-line tile rows (for_each_row): 384 -> 368 us with scalar taps
-#define VIP_ADA_UNROLL 1
-#endif
-
 namespace vip {
+
+// Outputs per thread: 8 need ~170 VGPRs (per-output centre/offset floats, accumulators,
+// pipelined LUT reads) -> 8 waves; 4 fit 128 -> 16 waves
+constexpr int kAdaP = 4;
+constexpr bool kAdaUnroll = true;  // straight-line tile rows (for_each_row): 384 -> 368 us with scalar taps
 
 // Separable box sums need VRB (TH x VW words) after the plane and VW u16 of VG in each
 // plane row's unused tail (S - VW words): true up to R = 8 at 16 waves.
@@ -33,7 +31,7 @@ constexpr bool adaptive_vbox() {
 
 // NE: LUT entries in LDS (1536 x 16 copies; or 512 x 32 copies, bank-conflict free, when
 // the colour LUT is exactly zero from entry 511 on -- sigma_color 30 underflows past
-// d = 431 -- with the index clamped to 511: one v_min_u32 per tap).
+// d = 431 -- with the index clamped to 511).
 // SAT (NE = 512, 32 copies): the index clamp costs no instruction -- the LUT address is
 // one v_mad_legacy_u16 with the clamp bit, min(d*128 + B0 + 4c, 65535), in place of the
 // v_lshl_or, and every d > 511 saturates onto entry (511, copy 31), an exact zero (the
@@ -46,7 +44,7 @@ constexpr int ada_lut_words() { return NE * (NE < 1536 ? 32 : 16) + (SAT ? kAdaS
 // The kernel body; MULTI: a multi-frame launch (adaptive_frames_kernel, as bilateral_body)
 template <int R, int WAVES, bool FMA, int P, int NE, bool SAT, bool MULTI>
 __device__ __forceinline__ void adaptive_body(const StencilArgs& a) {
-    static_assert(!SAT || NE == 512, "SAT: 512 entries x 32 copies");
+    static_assert(SAT ? NE == 512 : NE == 1536, "SAT: 512 entries x 32 copies; else the full LUT");
     using G = Geom<R, P>;
     constexpr int NT = WAVES * 64;
     constexpr int TH = WAVES * 4;
@@ -64,7 +62,7 @@ __device__ __forceinline__ void adaptive_body(const StencilArgs& a) {
     constexpr bool VBOX = adaptive_vbox<R, P, WAVES, ada_lut_words<NE, SAT>()>();
     // straight-line rows where the separable box sums apply (R <= 8); the larger
     // radii keep the row loop (code size and build time)
-    constexpr bool ROW_UNROLL = VIP_ADA_UNROLL != 0 && VBOX;
+    constexpr bool ROW_UNROLL = kAdaUnroll && VBOX;
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     uint32_t* const lut = lds + (SAT ? kAdaSatT / 4 : 0);
     constexpr int COPIES = NE < 1536 ? 32 : 16;
@@ -77,11 +75,7 @@ __device__ __forceinline__ void adaptive_body(const StencilArgs& a) {
     const int tx = lane & 15;
     const int ty = wave * 4 + (lane >> 4);
     const uint32_t lane16 = (uint32_t)(lane & (COPIES - 1)) << 2;
-#if VIP_SAT_SHARE31  // measurement knob: lanes 30/31 share copy 30, copy 31's bank holds only the saturation target
-    const uint32_t sbias = (uint32_t)kAdaSatB0 + (COPIES == 32 && lane16 == 124u ? 120u : lane16);
-#else
     const uint32_t sbias = (uint32_t)kAdaSatB0 + lane16;  // SAT: register bias of the address
-#endif
     const char* const lut_bytes = reinterpret_cast<const char*>(lut);
 
     int tile = blockIdx.x;  // persistent: items blockIdx.x + k * gridDim.x (item_tile)
@@ -274,19 +268,18 @@ __device__ __forceinline__ void adaptive_body(const StencilArgs& a) {
                     // dist = |(n0-c0)-o0| + |(n1-c1)-o1| + |(n2-c2)-o2|; (float)(n-c) == f_n - f_c exactly.
                     // Index int(dist) <= 1530 -> word d*16 + (lane & 15) of the 1536 x 16 LUT.
                     auto widx = [&](uint32_t, f2 n01, f2 n21, int i, int) {
-                        // scalar subtracts here and scalar fma accumulation (row_taps PK =
-                        // false): the packed forms (v_pk_add_f32 {b, g} pairs, v_pk_fma_f32
-                        // accumulation) measured 446 us per 4K frame against 381 us
+                        // scalar subtracts here and scalar fma accumulation (row_taps): the
+                        // packed forms (v_pk_add_f32 {b, g} pairs, v_pk_fma_f32 accumulation)
+                        // measured 446 us per 4K frame against 381 us
                         const float d0 = (n01.x - c0f[i]) - o0[i];
                         const float d1 = (n01.y - c1f[i]) - o1[i];
                         const float d2 = (n21.x - c2f[i]) - o2[i];
                         const float dist = (__builtin_fabsf(d0) + __builtin_fabsf(d1)) + __builtin_fabsf(d2);
                         uint32_t d = (uint32_t)dist;
                         if constexpr (SAT) return sat_addr(d, 128u, sbias) + (uint32_t)(kAdaSatT - kAdaSatB0);
-                        if constexpr (NE < 1536) d = d < NE - 1 ? d : NE - 1;
-                        return (d << (COPIES == 32 ? 7 : 6)) | lane16;
+                        return (d << 6) | lane16;
                     };
-                    row_taps<HW, G::L, C0, NC, FMA, false, P, false, decltype(widx)&, false, VIP_PIPE_DEPTH, SAT>(
+                    row_taps<HW, G::L, C0, NC, FMA, P, false, decltype(widx)&, false, kPipeDepth, SAT>(
                         plane, plane, row_off, wsv, lut_bytes, widx, a01, a2k);
                     if constexpr (ROW_UNROLL) fence_accumulators(a01, a2k);
             });
@@ -313,18 +306,11 @@ __global__ __launch_bounds__(WAVES * 64) void adaptive_frames_kernel(const Stenc
     adaptive_body<R, WAVES, FMA, P, NE, SAT, true>(a);
 }
 
-#ifndef VIP_ADA_SHORT_LUT
-#define VIP_ADA_SHORT_LUT 0
-#endif
-#ifndef VIP_ADA_SAT  // 512 x 32 conflict-free LUT behind the saturating address
-#define VIP_ADA_SAT 1
-#endif
-
-template <int R, bool FMA, int NE, bool SAT = false>
-static int launch_adaptive_ne(const StencilArgs& a, hipStream_t stream) {
-    // P = 8 outputs per thread needs ~170 VGPRs (per-output centre/offset floats,
-    // accumulators, pipelined LUT reads) -> 8 waves; P = 4 fits 128 -> 16 waves
-    constexpr int P = VIP_ADA_P;
+// SAT: the 512 x 32 conflict-free LUT behind the saturating address; else 1536 x 16
+template <int R, bool FMA, bool SAT>
+static int launch_adaptive_lut(const StencilArgs& a, hipStream_t stream) {
+    constexpr int P = kAdaP;
+    constexpr int NE = SAT ? 512 : 1536;
     using G = Geom<R, P>;
     constexpr int LUTW = ada_lut_words<NE, SAT>();
     constexpr int WAVES = pick_waves<R, 1, P == 8 ? 8 : 16, LUTW, P>();
@@ -367,11 +353,8 @@ static int launch_adaptive_ne(const StencilArgs& a, hipStream_t stream) {
 
 template <int R, bool FMA>
 static int launch_adaptive_r(const StencilArgs& a, hipStream_t stream) {
-    if constexpr (VIP_ADA_SAT != 0)
-        if (a.lut_nonzero <= 511) return launch_adaptive_ne<R, FMA, 512, true>(a, stream);
-    if constexpr (VIP_ADA_SHORT_LUT != 0)
-        if (a.lut_nonzero <= 511) return launch_adaptive_ne<R, FMA, 512>(a, stream);
-    return launch_adaptive_ne<R, FMA, 1536>(a, stream);
+    if (a.lut_nonzero <= 511) return launch_adaptive_lut<R, FMA, true>(a, stream);
+    return launch_adaptive_lut<R, FMA, false>(a, stream);
 }
 
 template <bool FMA>

@@ -40,20 +40,12 @@ __device__ __forceinline__ void vip_rt_stamp(int k) {
 #define VIP_RT_STAMP(k)
 #endif
 
-#ifndef VIP_BIL_UNROLL_MAX_R
-#define VIP_BIL_UNROLL_MAX_R 15
-#endif
-#ifndef VIP_BIL_PIPE_DEPTH  // plain bilateral: LUT reads this many neighbour columns ahead
-#define VIP_BIL_PIPE_DEPTH VIP_PIPE_DEPTH
-#endif
-#ifndef VIP_BIL_RCP  // epilogue: one exact reciprocal per output instead of 3 IEEE divides
-#define VIP_BIL_RCP 1
-#endif
-// NE: colour-LUT entries held in LDS. 768 (every L1 distance), or 32 when the
-// handle's LUT is exactly zero from entry 31 on (small sigma_color: the texture
-// filter's JBF has sigma_color sqrt(3), nonzero up to d = 24): the distance is then
-// clamped to 31 (one v_min_u32 per tap) and the 32-copy table takes 4 KiB.
-// FOLD (with SAT, NE = 32): one table per distinct squared tap distance r^2, holding
+constexpr int kBilUnrollMaxR = 15;  // straight-line tile rows (for_each_row) up to this radius: all
+constexpr bool kBilRcp = true;      // epilogue: one exact reciprocal per output instead of 3 IEEE divides
+// NE: colour-LUT entries held in LDS. 768 (every L1 distance), or the folded tables' 32.
+// FOLD (with SAT, NE = 32; the handle's LUT is exactly zero from entry 31 on -- small
+// sigma_color: the texture filter's JBF has sigma_color sqrt(3), nonzero up to d = 24):
+// one table per distinct squared tap distance r^2, holding
 // the full weight RN(ws(r^2) * wc[d]) -- the same float product the unfolded taps
 // form, so bit-identical -- addressed by the tap's compile-time table offset (the
 // ds_read immediate) behind the saturating address (SatLut, vip_stencil.hpp): per tap
@@ -67,13 +59,6 @@ struct FoldRank {  // table index of tap (|ky|, |kx|)
             for (int x = 0; x <= R; ++x) t[y * (R + 1) + x] = disc_r2_rank(R, x * x + y * y);
     }
 };
-// VIP_BIL_MIN_WPE (build knob, experiments): at least this many waves per SIMD, i.e. a
-// VGPR cap of 512 / N, so that a smaller workgroup leaves registers for a second kernel
-#ifdef VIP_BIL_MIN_WPE
-#define VIP_BIL_WPE_ATTR __attribute__((amdgpu_waves_per_eu(VIP_BIL_MIN_WPE)))
-#else
-#define VIP_BIL_WPE_ATTR
-#endif
 // The kernel body; MULTI: a multi-frame launch (bilateral_frames_kernel), whose tiles run
 // from one frame into the next (StencilArgs::nframes). The one-frame kernel compiles with
 // MULTI = false, to exactly the code it had before multi-frame launches existed.
@@ -82,17 +67,16 @@ __device__ __forceinline__ void bilateral_body(const StencilArgs& a) {
     using G = Geom<R, P, TPR>;
     constexpr int NT = WAVES * 64;
     constexpr int TH = WAVES * G::RPW;
-    constexpr bool ROW_UNROLL = R <= VIP_BIL_UNROLL_MAX_R;  // straight-line rows (for_each_row)
+    constexpr bool ROW_UNROLL = R <= kBilUnrollMaxR;  // straight-line rows (for_each_row)
     constexpr int ROWS = TH + 2 * R;
     constexpr int PLANE = ROWS * G::S;
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     uint32_t* const lut = lds;
     constexpr int NTAB = FOLD ? disc_r2_count(R) : 1;
-    static_assert(!FOLD || (SAT && NE == 32 && COPIES == sat_fold_copies<R>()), "folded tables: saturating address");
-    // SAT: tables from byte SL::T, planes at SL::PL (folded: one table per r^2, d <= DZ;
-    // unfolded: the colour LUT, d <= 511, times the spatial weight per tap)
-    using SL = SatLut<R, 4 * (JOINT ? 2 : 1) * PLANE, FOLD ? disc_r2_count(R) : 1, FOLD ? kSatFoldDz : 511,
-                      FOLD ? COPIES : 32>;
+    static_assert(SAT == FOLD, "the saturating address serves the folded tables only");
+    static_assert(!FOLD || (NE == 32 && COPIES == sat_fold_copies<R>()), "folded tables: saturating address");
+    // SAT: one table per r^2 (d <= DZ) from byte SL::T, planes at SL::PL
+    using SL = SatLut<R, 4 * (JOINT ? 2 : 1) * PLANE, disc_r2_count(R), kSatFoldDz, COPIES>;
     uint32_t* const gplane = SAT ? lds + SL::PL / 4 : lds + NTAB * NE * COPIES;
     uint32_t* const splane = JOINT ? gplane + PLANE : gplane;
 
@@ -102,11 +86,7 @@ __device__ __forceinline__ void bilateral_body(const StencilArgs& a) {
     const int tx = lane % TPR;
     const int ty = wave * G::RPW + lane / TPR;
     const uint32_t lane4 = (uint32_t)(lane & (COPIES - 1)) << 2;  // this lane's LUT copy
-#if VIP_SAT_SHARE31  // measurement knob: lanes 30/31 share copy 30, copy 31's bank holds only the saturation target
-    const uint32_t sbias = (uint32_t)SL::B0 + (SAT && COPIES == 32 && lane4 == 124u ? 120u : lane4);
-#else
     const uint32_t sbias = (uint32_t)SL::B0 + lane4;                // SAT: register bias of the address
-#endif
     const char* const lut_bytes = reinterpret_cast<const char*>(lut);
 
     VIP_RT_STAMP(0);
@@ -171,25 +151,20 @@ __device__ __forceinline__ void bilateral_body(const StencilArgs& a) {
                     // colour weight address: v_sad_u8 (|db|+|dg|+|dr|) -> word d*COPIES + lane copy
                     auto widx = [&](uint32_t g, f2, f2, int i, int kx) {
                         uint32_t d = __builtin_amdgcn_sad_u8(g, ctr[i], 0u);
-                        if constexpr (SAT) {  // min(d*S + bias, 65535) + table offset (immediate)
-                            uint32_t off = (uint32_t)(SL::T - SL::B0);
-                            if constexpr (FOLD) {
-                                constexpr FoldRank<R> rank;
-                                off += 4u * COPIES * rank.t[aky * (R + 1) + (kx < 0 ? -kx : kx)];
-                            }
-                            return sat_addr(d, SL::S, sbias) + off;
+                        if constexpr (FOLD) {  // min(d*S + bias, 65535) + table offset (immediate)
+                            constexpr FoldRank<R> rank;
+                            return sat_addr(d, SL::S, sbias) + (uint32_t)(SL::T - SL::B0) +
+                                   4u * COPIES * rank.t[aky * (R + 1) + (kx < 0 ? -kx : kx)];
                         }
-                        if constexpr (NE < 768) d = d < NE - 1 ? d : NE - 1;
                         return (d << (COPIES == 32 ? 7 : 6)) | lane4;
                     };
-                    row_taps<HW, G::L, C0, NC, FMA, false, P, JOINT, decltype(widx)&, FOLD,
-                             JOINT ? VIP_PIPE_DEPTH : VIP_BIL_PIPE_DEPTH, SAT>(
+                    row_taps<HW, G::L, C0, NC, FMA, P, JOINT, decltype(widx)&, FOLD, kPipeDepth, SAT>(
                         gplane, splane, row_off, wsv, lut_bytes, widx, a01, a2k);
                     if constexpr (ROW_UNROLL) fence_accumulators(a01, a2k);
             });
 
             uint32_t o[P];
-            finish_outputs<P, VIP_BIL_RCP != 0>(a01, a2k, o);
+            finish_outputs<P, kBilRcp>(a01, a2k, o);
             store_px_to(a, JOINT ? a.dst : frame_dst<MULTI>(a, tile), ty0 + ty, tx0 + tx * P, o);
         }
         VIP_STAMP(it, 1);
@@ -208,88 +183,38 @@ __device__ __forceinline__ void bilateral_body(const StencilArgs& a) {
 
 template <int R, int WAVES, bool JOINT, bool FMA, int COPIES, int P, int NE = 768, bool FOLD = false, int TPR = 16,
           bool SAT = false>
-__global__ __launch_bounds__(WAVES * 64) VIP_BIL_WPE_ATTR void bilateral_kernel(const StencilArgs a) {
+__global__ __launch_bounds__(WAVES * 64) void bilateral_kernel(const StencilArgs a) {
     bilateral_body<R, WAVES, JOINT, FMA, COPIES, P, NE, FOLD, TPR, SAT, false>(a);
 }
 // multi-frame launches (vip_bilateral_run_rows_batch; plain filter, radius <= kBatchMaxRadius)
 template <int R, int WAVES, bool JOINT, bool FMA, int COPIES, int P, int NE = 768, bool FOLD = false, int TPR = 16,
           bool SAT = false>
-__global__ __launch_bounds__(WAVES * 64) VIP_BIL_WPE_ATTR void bilateral_frames_kernel(const StencilArgs a) {
+__global__ __launch_bounds__(WAVES * 64) void bilateral_frames_kernel(const StencilArgs a) {
     bilateral_body<R, WAVES, JOINT, FMA, COPIES, P, NE, FOLD, TPR, SAT, true>(a);
 }
 
 // The joint kernel holds two tile planes; when the full 32-copy LUT leaves room for
 // fewer than 16 waves, a 16-copy LUT (lanes l and l+16 of a half-wave share a copy:
-// at most 2-way bank conflicts) is used if it buys more waves (VIP_JBF_LUT16=0 disables).
-#ifndef VIP_JBF_LUT16
-#define VIP_JBF_LUT16 1
-#endif
-#ifndef VIP_JBF_MAXW
-#define VIP_JBF_MAXW 16
-#endif
+// at most 2-way bank conflicts) is used if it buys more waves.
+constexpr bool kJbfLut16 = true;
 // Outputs per thread: 8 for the plain filter. The joint filter's second plane and
 // prefetch registers push 8 outputs past 128 VGPRs as the radius grows (spilled
 // VGPRs: 0 up to R = 3, 1 at R = 4, 14 at R = 7, 36 at R = 8, 69+ beyond); 8 outputs
-// still win up to R = 7 (measured: r=4 84 -> 79 us, r=7 214 -> 206 us), 4 above.
-#ifndef VIP_JBF_P8_MAX_R
-#define VIP_JBF_P8_MAX_R 7
-#endif
-#ifndef VIP_BIL_P
-#define VIP_BIL_P 8
-#endif
+// still win up to R = 7 (measured: r=4 84 -> 79 us, r=7 214 -> 206 us), 4 above
+// (round 6, texture JBF at 4K, profiles/r06_jbf_p8_big_r_ab.txt: R = 8 239.7-240.0 us with
+// 4 outputs on 16 waves against 266.4-266.6 with 8 on 12 waves).
+constexpr int kJbfP8MaxR = 7;
+constexpr int kBilP = 8;
 template <int R, int PLANES>
-constexpr int outputs_per_thread() { return PLANES == 2 ? (R <= VIP_JBF_P8_MAX_R ? 8 : 4) : VIP_BIL_P; }
+constexpr int outputs_per_thread() { return PLANES == 2 ? (R <= kJbfP8MaxR ? 8 : 4) : kBilP; }
 template <int R, int PLANES>
 constexpr int lut_copies() {
     constexpr int P = outputs_per_thread<R, PLANES>();
-    if (!VIP_JBF_LUT16 || PLANES == 1) return 32;
-    return pick_waves<R, PLANES, VIP_JBF_MAXW, 768 * 16, P>() > pick_waves<R, PLANES, 16, 768 * 32, P>() ? 16 : 32;
-}
-// Plain filter above radius 8 (the row-loop radii, C5's r=15): wave cap (build knob;
-// 12 waves allow 168 VGPRs, no spills)
-#ifndef VIP_BIL_BIG_MAXW
-#define VIP_BIL_BIG_MAXW 16
-#endif
-// Joint filter with 8 outputs per thread beyond radius 7 (VIP_JBF_P8_MAX_R > 7): wave cap
-// (12 waves allow 168 VGPRs: no spills at R = 8..10). Measured round 6 on the texture JBF
-// (profiles/r06_jbf_p8_big_r_ab.txt, 4K, interleaved): R = 8 239.7-240.0 us with 4 outputs
-// on 16 waves against 266.4-266.6 (8 on 12 waves) and 285.9-286.6 (8 on 8); R = 10 379-380
-// against 420 and 449. The default stays 4 outputs beyond radius 7.
-#ifndef VIP_JBF_P8_BIG_MAXW
-#define VIP_JBF_P8_BIG_MAXW 12
-#endif
-template <int R, int PLANES>
-constexpr int max_waves() {
-    return PLANES == 2 ? (R > 7 && R <= VIP_JBF_P8_MAX_R ? VIP_JBF_P8_BIG_MAXW : VIP_JBF_MAXW)
-                       : (R > 8 ? VIP_BIL_BIG_MAXW : 16);
+    if (!kJbfLut16 || PLANES == 1) return 32;
+    return pick_waves<R, PLANES, 16, 768 * 16, P>() > pick_waves<R, PLANES, 16, 768 * 32, P>() ? 16 : 32;
 }
 
-#ifndef VIP_JBF_WIDE  // joint kernel on wide tiles with the 32-copy LUT (measurement knob)
-#define VIP_JBF_WIDE 0
-#endif
-#ifndef VIP_JBF_WIDE_MAX_R
-#define VIP_JBF_WIDE_MAX_R 8
-#endif
-
-// Plain kernel on the 512-entry saturating-address LUT (SatLut, 64 KiB, v_mad_legacy_u16
-// in place of the v_lshl_or) when the colour LUT allows it. Measured slower, so off: C2
-// 172.3 -> 175.4 us, the C5 slab 3198 -> 3296 us (profiles/r03_sat_variants.txt).
-#ifndef VIP_BIL_SAT
-#define VIP_BIL_SAT 0
-#endif
-
-// Joint kernel on the 512-entry saturating-address LUT (SatLut, 32 copies: no bank
-// conflicts) in place of the 16-copy 768-entry LUT, when the colour LUT is zero past 511
-// (sigma_color 30: past 432) and the tables leave as many waves (measurement knob).
-#ifndef VIP_JBF_SAT
-#define VIP_JBF_SAT 0
-#endif
-
-#ifndef VIP_JBF_SHORT_LUT  // joint kernel: 32-entry clamped LUT when the colour LUT allows it
-#define VIP_JBF_SHORT_LUT 0
-#endif
-
-// Small frames (plain filter, R <= VIP_BIL_SMALL_MAX_R): a frame with fewer 128 x 64
+// Small frames (plain filter, R <= kBilSmallMaxR): a frame with fewer 128 x 64
 // tiles than CUs leaves CUs idle (C1's 512 x 512 lenna: 32 tiles on 256 CUs; a 270-row
 // slab of the 4K frame at 8 GPUs: 150). Two ways to spread it: fewer waves per workgroup
 // (8 or 4: 128 x 32 / 128 x 16 tiles, more CUs busy, fewer waves per SIMD), and the
@@ -301,12 +226,8 @@ constexpr int max_waves() {
 // work = 1 for 8 outputs per thread, kWideWork for 4 (half the taps plus the extra byte
 // conversions and apron rows). vip_bilateral_set_waves / VIP_BIL_WAVES and
 // vip_bilateral_set_wide / VIP_BIL_WIDE force either.
-#ifndef VIP_BIL_SMALL_MAX_R
-#define VIP_BIL_SMALL_MAX_R 8
-#endif
-#ifndef VIP_BIL_WIDE_WORK
-#define VIP_BIL_WIDE_WORK 0.55f
-#endif
+constexpr int kBilSmallMaxR = 8;
+constexpr float kWideWork = 0.55f;
 struct Tiling {
     int waves;
     bool wide;
@@ -334,81 +255,71 @@ inline Tiling small_frame_tiling(int width, int out_rows, int inflight = 1, int 
             if (forced && cand[i] != forced) continue;
             const int th = cand[i] * rpw;
             const long long tiles = tiles_x * ((out_rows + th - 1) / th) * (nframes > 1 ? nframes : 1);
-            const float t = (float)((tiles + cus - 1) / cus) * cand[i] * cost[i] * (wide ? VIP_BIL_WIDE_WORK : 1.f);
+            const float t = (float)((tiles + cus - 1) / cus) * cand[i] * cost[i] * (wide ? kWideWork : 1.f);
             if (first || t < best_t) best = Tiling{cand[i], wide != 0}, best_t = t, first = false;
         }
     }
     return best;
 }
 
-template <int R, bool JOINT, bool FMA, int NE, bool FOLD, int WAVES, bool WIDE = false, bool SAT = false>
+// The launch with its wave count chosen. FOLD: the joint filter's folded tables behind the
+// saturating address (SatLut), 32 entries; otherwise the 768-entry colour LUT. WIDE: 256-pixel
+// tiles (plain filter only).
+template <int R, bool JOINT, bool FMA, bool FOLD, int WAVES, bool WIDE = false>
 static int launch_bilateral_w(const StencilArgs& a, hipStream_t stream);
 
-// LDS of a SAT launch (the saturating-address tables and the planes)
-template <int R, int WAVES, int PLANES, int P, bool FOLD>
+// LDS of a folded launch (the saturating-address tables and the planes)
+template <int R, int WAVES, int PLANES, int P>
 constexpr int sat_lds_bytes() {
-    return SatLut<R, 4 * PLANES * (WAVES * Geom<R, P>::RPW + 2 * R) * Geom<R, P>::S, FOLD ? disc_r2_count(R) : 1,
-                  FOLD ? kSatFoldDz : 511, FOLD ? sat_fold_copies<R>() : 32>::BYTES;
+    return SatLut<R, 4 * PLANES * (WAVES * Geom<R, P>::RPW + 2 * R) * Geom<R, P>::S, disc_r2_count(R), kSatFoldDz,
+                  sat_fold_copies<R>()>::BYTES;
 }
-template <int R, int PLANES, int MAXW, int P, bool FOLD>
+template <int R, int PLANES, int P>
 constexpr int pick_waves_sat() {
-    if (MAXW >= 16 && sat_lds_bytes<R, 16, PLANES, P, FOLD>() <= kLdsBudget) return 16;
-    if (MAXW >= 12 && sat_lds_bytes<R, 12, PLANES, P, FOLD>() <= kLdsBudget) return 12;
-    if (MAXW >= 8 && sat_lds_bytes<R, 8, PLANES, P, FOLD>() <= kLdsBudget) return 8;
-    return sat_lds_bytes<R, 4, PLANES, P, FOLD>() <= kLdsBudget ? 4 : 0;
+    if (sat_lds_bytes<R, 16, PLANES, P>() <= kLdsBudget) return 16;
+    if (sat_lds_bytes<R, 12, PLANES, P>() <= kLdsBudget) return 12;
+    if (sat_lds_bytes<R, 8, PLANES, P>() <= kLdsBudget) return 8;
+    return sat_lds_bytes<R, 4, PLANES, P>() <= kLdsBudget ? 4 : 0;
 }
 
-template <int R, bool JOINT, bool FMA, int NE, bool FOLD = false, bool SAT = false>
-static int launch_bilateral_ne(const StencilArgs& a, hipStream_t stream) {
+template <int R, bool JOINT, bool FMA, bool FOLD>
+static int launch_bilateral_lut(const StencilArgs& a, hipStream_t stream) {
     constexpr int PLANES = JOINT ? 2 : 1;
     constexpr int P = outputs_per_thread<R, PLANES>();
-    constexpr int COPIES = FOLD ? sat_fold_copies<R>() : NE < 768 ? 32 : lut_copies<R, PLANES>();
-    constexpr int LUTW = (FOLD ? disc_r2_count(R) : 1) * NE * COPIES;
-    constexpr int WAVES = SAT ? pick_waves_sat<R, PLANES, max_waves<R, PLANES>(), P, FOLD>()
-                              : pick_waves<R, PLANES, max_waves<R, PLANES>(), LUTW, P>();
+    constexpr int WAVES = FOLD ? pick_waves_sat<R, PLANES, P>()
+                               : pick_waves<R, PLANES, 16, 768 * lut_copies<R, PLANES>(), P>();
     static_assert(WAVES > 0, "tile does not fit LDS");
-    if constexpr (SAT) {
-        return launch_bilateral_w<R, JOINT, FMA, NE, FOLD, WAVES, false, true>(a, stream);
-    } else {
-#if VIP_JBF_WIDE
-        // joint filter on wide tiles (P = 4, one 256-pixel row per wave): two planes of
-        // 16 + 2R rows leave room for the 32-copy (bank-conflict free) LUT at 16 waves
-        if constexpr (JOINT && !FOLD && NE == 768 && R <= VIP_JBF_WIDE_MAX_R)
-            return launch_bilateral_w<R, JOINT, FMA, NE, FOLD, 16, true>(a, stream);
-#endif
-        if constexpr (!JOINT && !FOLD && NE == 768 && WAVES == 16 && R <= VIP_BIL_SMALL_MAX_R) {
-            const Tiling t = small_frame_tiling(a.width, a.out_rows, a.inflight, a.nframes);
-            if (t.wide) {
-                if (t.waves == 16) return launch_bilateral_w<R, JOINT, FMA, NE, FOLD, 16, true>(a, stream);
-                if (t.waves == 8) return launch_bilateral_w<R, JOINT, FMA, NE, FOLD, 8, true>(a, stream);
-                return launch_bilateral_w<R, JOINT, FMA, NE, FOLD, 4, true>(a, stream);
-            }
-            if (t.waves == 8) return launch_bilateral_w<R, JOINT, FMA, NE, FOLD, 8>(a, stream);
-            if (t.waves == 4) return launch_bilateral_w<R, JOINT, FMA, NE, FOLD, 4>(a, stream);
+    if constexpr (!JOINT && WAVES == 16 && R <= kBilSmallMaxR) {
+        const Tiling t = small_frame_tiling(a.width, a.out_rows, a.inflight, a.nframes);
+        if (t.wide) {
+            if (t.waves == 16) return launch_bilateral_w<R, JOINT, FMA, FOLD, 16, true>(a, stream);
+            if (t.waves == 8) return launch_bilateral_w<R, JOINT, FMA, FOLD, 8, true>(a, stream);
+            return launch_bilateral_w<R, JOINT, FMA, FOLD, 4, true>(a, stream);
         }
-        return launch_bilateral_w<R, JOINT, FMA, NE, FOLD, WAVES>(a, stream);
+        if (t.waves == 8) return launch_bilateral_w<R, JOINT, FMA, FOLD, 8>(a, stream);
+        if (t.waves == 4) return launch_bilateral_w<R, JOINT, FMA, FOLD, 4>(a, stream);
     }
+    return launch_bilateral_w<R, JOINT, FMA, FOLD, WAVES>(a, stream);
 }
 
-template <int R, bool JOINT, bool FMA, int NE, bool FOLD, int WAVES, bool WIDE, bool SAT>
+template <int R, bool JOINT, bool FMA, bool FOLD, int WAVES, bool WIDE>
 static int launch_bilateral_w(const StencilArgs& a, hipStream_t stream) {
+    static_assert(!FOLD || JOINT, "folded tables: the joint filter");
+    static_assert(!WIDE || !JOINT, "wide tiles: the plain filter");
     constexpr int PLANES = JOINT ? 2 : 1;
     constexpr int P = WIDE ? 4 : outputs_per_thread<R, PLANES>();
     constexpr int TPR = WIDE ? 64 : 16;  // threads per tile row
     using G = Geom<R, P, TPR>;
-    constexpr int COPIES = FOLD ? sat_fold_copies<R>()
-                                : NE < 768 || (WIDE && pick_waves<R, PLANES, WAVES, 768 * 32, P, TPR>() == WAVES)
-                                      ? 32
-                                      : lut_copies<R, PLANES>();
-    constexpr int LUTW = (FOLD ? disc_r2_count(R) : 1) * NE * COPIES;
+    constexpr int NE = FOLD ? kFoldEntries : 768;
+    constexpr int COPIES = FOLD ? sat_fold_copies<R>() : lut_copies<R, PLANES>();
     constexpr int TH = WAVES * G::RPW;
-    constexpr int LDS = SAT ? sat_lds_bytes<R, WAVES, PLANES, P, FOLD>() : lds_bytes<R, WAVES, PLANES, LUTW, P, TPR>();
+    constexpr int LDS = FOLD ? sat_lds_bytes<R, WAVES, PLANES, P>() : lds_bytes<R, WAVES, PLANES, NE * COPIES, P, TPR>();
     static_assert(LDS <= kLdsBudget, "tile does not fit LDS");
-    static_assert(!SAT || TPR == 16, "SAT: 128-pixel tiles");
+    constexpr bool SAT = FOLD;  // the kernel's saturating address (absolute LDS addresses)
     auto kern = bilateral_kernel<R, WAVES, JOINT, FMA, COPIES, P, NE, FOLD, TPR, SAT>;
     static std::atomic<unsigned long long> attr_devs{0};
     const bool multi = !JOINT && a.nframes > 1;
-    if constexpr (!JOINT && !FOLD && R <= kBatchMaxRadius) {
+    if constexpr (!JOINT && R <= kBatchMaxRadius) {
         if (multi) {
             kern = bilateral_frames_kernel<R, WAVES, JOINT, FMA, COPIES, P, NE, FOLD, TPR, SAT>;
             static std::atomic<unsigned long long> attr_devs_frames{0};
@@ -439,30 +350,12 @@ static int launch_bilateral_w(const StencilArgs& a, hipStream_t stream) {
     return (int)hipGetLastError();
 }
 
-template <int R>
-constexpr bool jbf_sat_fits() {
-    constexpr int P = outputs_per_thread<R, 2>();
-    return pick_waves_sat<R, 2, max_waves<R, 2>(), P, false>() >=
-           pick_waves<R, 2, max_waves<R, 2>(), 768 * lut_copies<R, 2>(), P>();
-}
-
 template <int R, bool JOINT, bool FMA>
 static int launch_bilateral_r(const StencilArgs& a, hipStream_t stream) {
-    if constexpr (!JOINT && VIP_BIL_SAT) {  // plain filter, 128-pixel 16-wave tiles: 512 x 32 LUT (SatLut)
-        if (a.lut_nonzero <= 511) {
-            const Tiling t = R <= VIP_BIL_SMALL_MAX_R ? small_frame_tiling(a.width, a.out_rows, a.inflight, a.nframes)
-                                                      : Tiling{16, false};
-            if (t.waves == 16 && !t.wide) return launch_bilateral_ne<R, JOINT, FMA, 768, false, true>(a, stream);
-        }
-    }
     if constexpr (JOINT && R <= kSatMaxR)  // saturating-address folded tables (SatLut)
         if (a.fold && a.lut_nonzero <= SatLut<R, 0, disc_r2_count(R), kSatFoldDz, sat_fold_copies<R>()>::DZ)
-            return launch_bilateral_ne<R, JOINT, FMA, 32, true, true>(a, stream);
-    if constexpr (JOINT && VIP_JBF_SHORT_LUT)
-        if (a.lut_nonzero <= 31) return launch_bilateral_ne<R, JOINT, FMA, 32>(a, stream);
-    if constexpr (JOINT && VIP_JBF_SAT && jbf_sat_fits<R>())
-        if (!a.fold && a.lut_nonzero <= 511) return launch_bilateral_ne<R, JOINT, FMA, 768, false, true>(a, stream);
-    return launch_bilateral_ne<R, JOINT, FMA, 768>(a, stream);
+            return launch_bilateral_lut<R, JOINT, FMA, true>(a, stream);
+    return launch_bilateral_lut<R, JOINT, FMA, false>(a, stream);
 }
 
 template <bool JOINT, bool FMA>

@@ -29,18 +29,12 @@ constexpr int kLdsBudget = 160 * 1024;
 // work with 16-copy tables (sat_fold_copies), bit-exact, but measured slower than the
 // 768 x 16 LUT those radii keep: texture JBF R = 7 186.6 -> 207.8 us, R = 8 242.0 -> 274.7
 // (profiles/r06_jbf_fold16_ab.txt)
-#ifndef VIP_JBF_SAT_MAX_R
-#define VIP_JBF_SAT_MAX_R 6
-#endif
-constexpr int kSatMaxR = VIP_JBF_SAT_MAX_R;
+constexpr int kSatMaxR = 6;
 constexpr int kFoldEntries = 32;  // the handle's folded tables hold d < 32 (zeros past the colour LUT's end)
-// Largest distance the folded SatLut stores (measurement knob). A larger DZ (51 at R = 4,
-// with 64-entry tables) means fewer saturated lanes and fewer 2-way conflicts on copy 31's
-// bank, but measured no faster: C4 frame 674.8 -> 678.9 us (profiles/r03_sat_variants.txt).
-#ifndef VIP_JBF_SAT_DZMAX
-#define VIP_JBF_SAT_DZMAX (kFoldEntries - 1)
-#endif
-constexpr int kSatFoldDz = VIP_JBF_SAT_DZMAX;
+// Largest distance the folded SatLut stores. A larger DZ (51 at R = 4, with 64-entry
+// tables) means fewer saturated lanes and fewer 2-way conflicts on copy 31's bank, but
+// measured no faster: C4 frame 674.8 -> 678.9 us (profiles/r03_sat_variants.txt).
+constexpr int kSatFoldDz = kFoldEntries - 1;
 static_assert(kSatFoldDz < kFoldEntries, "folded tables hold d < kFoldEntries");
 
 // Folded joint-bilateral LUT behind a saturating address (SAT). One table per distinct
@@ -58,9 +52,9 @@ static_assert(kSatFoldDz < kFoldEntries, "folded tables hold d < kFoldEntries");
 // 3 v_fma, v_add (the 32-copy reads stay bank-conflict free; lanes that saturate read one
 // broadcast word). T = B0 rounded up to 16 keeps the immediate small and >= 0; the tile
 // planes (PB bytes) go below the tables when they fit under B0, else after them.
-// NTAB_ = 1, DZMAX = 511: the unfolded colour LUT of the plain filter (zero from d <= 511,
-// e.g. sigma_color 30: zero from 432) as 512 entries x 32 copies -- 64 KiB instead of 96,
-// the v_lshl_or of the address replaced by the (fast-class) v_mad_legacy_u16.
+// NTAB_ = 1, DZMAX = 511: an unfolded colour LUT (zero from d <= 511, e.g. sigma_color 30:
+// zero from 432) as 512 entries x 32 copies -- the adaptive kernel's table (kAdaSatB0,
+// vip_adaptive.hip); the bilateral kernels measured slower on it and use the folded form only.
 // COPIES_ (round 6): 16 instead of 32 copies per table halve S, so the 16-bit address reaches
 // twice the distances -- the folded tables of radius 7 and 8 (24 and 30 of them) then still
 // hold d <= 31 >= 25, the texture JBF's zero point, where 32 copies stop at 21 and 17. Lanes l
@@ -172,9 +166,6 @@ inline int persistent_blocks(int tiles, int free_cus = 0) {
 
 constexpr int lut_words(bool adaptive) { return adaptive ? 1536 * 16 : 768 * 32; }
 
-#ifndef VIP_TAIL_SPLIT  // build knob: 0 runs the last round's tiles whole
-#define VIP_TAIL_SPLIT 1
-#endif
 // A persistent launch of T tiles on B workgroups runs ceil(T / B) rounds; when the last
 // holds k = T mod B tiles, B - k workgroups idle through it while k run a whole tile each
 // (a C2 slab batch at 8 GPUs: 1,530 tiles on 248 workgroups, 6.17 rounds run as 7). The
@@ -194,7 +185,7 @@ static_assert(tail_shift(1530, 255, 16) == 0 && tail_shift(100, 100, 16) == 0, "
 static_assert(tail_shift(7 + 2 * 256, 256, 16) == 4 && tail_shift(7 + 2 * 256, 256, 12) == 2, "pieces divide WAVES");
 static_assert(tail_shift(200 + 256, 256, 16) == 0, "k > blocks / 2: whole tiles");
 inline void plan_tail(StencilArgs& a, int blocks, int waves) {
-    const int s = VIP_TAIL_SPLIT ? tail_shift(a.tiles_total, blocks, waves) : 0;
+    const int s = tail_shift(a.tiles_total, blocks, waves);
     a.tail_full = s ? a.tiles_total - a.tiles_total % blocks : a.tiles_total;
     a.tail_shift = s;
 }
@@ -207,9 +198,6 @@ inline void plan_tail(StencilArgs& a, int blocks, int waves) {
 __device__ __forceinline__ int xcd_tile(int slot, int total) {
     const int grid = (int)gridDim.x, b = (int)blockIdx.x;
     const int base = slot - b;
-#ifdef VIP_NO_XCD_MAP
-    return slot;
-#endif
     if ((grid & 7) != 0 || base + grid > total) return slot;
     return base + (b & 7) * (grid >> 3) + (b >> 3);
 }
@@ -358,13 +346,6 @@ struct TilePrefetch {
             const int sy = clampi(ty0 + a.src_row0 - R + r, a.row_lo, a.row_hi - 1);
             const uint8_t* row = img + (long long)sy * pitch;
             const int x = tx0 - G::L + 4 * gc;
-#ifdef VIP_ABL_NOLOAD  // timing ablation only (wrong output): no HBM reads, the apron included
-            if (true) {
-                raw[k][0] = (uint32_t)g * 0x01030507u;
-                raw[k][1] = (uint32_t)(g + x) * 0x07050301u;
-                raw[k][2] = (uint32_t)(g ^ sy) * 0x01010101u;
-            } else
-#endif
             if (a.aligned && x >= 0 && x + 3 < a.width) {
                 const uint32_t* w = reinterpret_cast<const uint32_t*>(row + 3 * x);
                 raw[k][0] = w[0];
@@ -455,12 +436,9 @@ struct SatStage {
 // min(d * s + bias, 65535) in one VALU op (the clamp bit saturates the u16 result);
 // the legacy encoding zeroes the destination's high half (checked on gfx950 by
 // microbench/sat_addr.hip, which also measures its issue rate in the tap mix).
-#ifndef VIP_SAT_INSN
-#define VIP_SAT_INSN "v_mad_legacy_u16"
-#endif
 __device__ __forceinline__ uint32_t sat_addr(uint32_t d, uint32_t s, uint32_t bias) {
     uint32_t r;
-    __asm__(VIP_SAT_INSN " %0, %1, %2, %3 clamp" : "=v"(r) : "v"(d), "s"(s), "v"(bias));
+    __asm__("v_mad_legacy_u16 %0, %1, %2, %3 clamp" : "=v"(r) : "v"(d), "s"(s), "v"(bias));
     return r;
 }
 
@@ -511,25 +489,21 @@ struct RowStream {
 // issue slots to the waves that are behind, so all reach the barrier together.
 // `band` is 0..3 (first quarter of the rows .. last quarter).
 __device__ __forceinline__ void set_progress_priority(int band) {
-#ifndef VIP_NO_PRIO_BANDS
     switch (band) {  // s_setprio takes an immediate; band is wave-uniform
         case 0: __builtin_amdgcn_s_setprio(3); break;
         case 1: __builtin_amdgcn_s_setprio(2); break;
         case 2: __builtin_amdgcn_s_setprio(1); break;
         default: __builtin_amdgcn_s_setprio(0); break;
     }
-#else
-    (void)band;
-#endif
 }
 
-// LUT-read lookahead of the tap loop, in neighbour columns (build knob).
-#ifndef VIP_PIPE_DEPTH
-#define VIP_PIPE_DEPTH 1
-#endif
+// LUT-read lookahead of the tap loop, in neighbour columns.
+constexpr int kPipeDepth = 1;
+// Columns between a row chunk's LDS read and its first use.
+constexpr int kRowLookahead = 4;
 
 // The tap loop of one tile row for the thread's kP outputs, software-pipelined
-// VIP_PIPE_DEPTH neighbour columns ahead: while column j's weights are
+// kPipeDepth neighbour columns ahead: while column j's weights are
 // accumulated, the colour-LUT reads of columns j+1..j+D are already in flight
 // (the LDS latency is hidden inside the wave, not only across waves).
 // `widx(g, n01, n21, i, kx)` returns the LDS byte address of the colour weight of
@@ -548,26 +522,19 @@ __device__ __forceinline__ void fence_accumulators(f2 (&a01)[P], f2 (&a2k)[P]) {
     for (int i = 0; i < P; ++i) __asm__ volatile("" : "+v"(a01[i]), "+v"(a2k[i]));
 }
 
-// PK: accumulate with v_pk_fma_f32 ({s0,s1} and {s2,sk} pairs). Measured on gfx950:
-// slower for every kernel (bilateral -10 %; adaptive 381 us scalar vs 446 us packed,
-// together with packed offset subtracts) -- VOP3P ops do not pair with the other
-// VALU work -- so both kernels use PK = false; kept as a knob.
 // TWO: separate guide and source planes (joint bilateral); otherwise one plane.
-#ifndef VIP_ROW_LOOKAHEAD
-#define VIP_ROW_LOOKAHEAD 4  // columns between a chunk's LDS read and its first use
-#endif
 // ABS: widx returns an absolute LDS byte address (the kernel's dynamic LDS starts at 0),
 // read through an address-space-3 pointer, so a constant part of it lands in the ds_read
 // immediate instead of a v_add of the LDS base.
-template <int HW, int L, int C0, int NC, bool FMA, bool PK, int P, bool TWO, class WIdx, bool FOLD = false,
-          int D = VIP_PIPE_DEPTH, bool ABS = false>
+template <int HW, int L, int C0, int NC, bool FMA, int P, bool TWO, class WIdx, bool FOLD = false,
+          int D = kPipeDepth, bool ABS = false>
 __device__ __forceinline__ void row_taps(const uint32_t* gplane, const uint32_t* splane, int row_off,
                                          const float (&wsv)[HW + 1], const char* lut, WIdx&& widx,
                                          f2 (&a01)[P], f2 (&a2k)[P]) {
     constexpr int NB = D + 1;            // ring of in-flight columns
     constexpr int J0 = L - HW;           // first neighbour column relative to the thread's P
     constexpr int J1 = L + P - 1 + HW;   // last
-    constexpr int LA = D + VIP_ROW_LOOKAHEAD;
+    constexpr int LA = D + kRowLookahead;
     static_assert(J0 >= 4 * C0 && J1 < 4 * (C0 + NC), "row chunk range");
     auto chunk = [](int j) constexpr { return (j - 4 * C0) >> 2; };
     constexpr int PRE = chunk(J0 + LA < J1 ? J0 + LA : J1);  // chunks read before the loop
@@ -581,13 +548,8 @@ __device__ __forceinline__ void row_taps(const uint32_t* gplane, const uint32_t*
         const uint32_t p = row.source(j - 4 * C0);
         const int b = (j - J0) % NB;
         n01[b].x = (float)(p & 0xffu);
-#ifdef VIP_ABL_CVT  // timing ablation only (wrong output): one byte conversion per column
-        n01[b].y = n01[b].x;
-        n21[b].x = n01[b].x;
-#else
         n01[b].y = (float)((p >> 8) & 0xffu);
         n21[b].x = (float)((p >> 16) & 0xffu);
-#endif
         n21[b].y = 1.0f;
 #pragma unroll
         for (int i = 0; i < P; ++i) {
@@ -612,13 +574,7 @@ __device__ __forceinline__ void row_taps(const uint32_t* gplane, const uint32_t*
             const int kx = j - L - i;
             if (kx < -HW || kx > HW) continue;
             const float w = FOLD ? wc[b][i] : wc[b][i] * wsv[kx < 0 ? -kx : kx];
-            if constexpr (FMA && PK) {
-                // v_pk_fma_f32: {s0,s1} += {b,g}*w and {s2,sk} += {r,1}*w; each half is an
-                // IEEE fma, and fma(1, w, sk) == sk + w exactly
-                const f2 w2 = {w, w};
-                a01[i] = __builtin_elementwise_fma(n01[b], w2, a01[i]);
-                a2k[i] = __builtin_elementwise_fma(n21[b], w2, a2k[i]);
-            } else if constexpr (FMA) {
+            if constexpr (FMA) {
                 a01[i].x = __builtin_fmaf(n01[b].x, w, a01[i].x);
                 a01[i].y = __builtin_fmaf(n01[b].y, w, a01[i].y);
                 a2k[i].x = __builtin_fmaf(n21[b].x, w, a2k[i].x);
@@ -630,9 +586,7 @@ __device__ __forceinline__ void row_taps(const uint32_t* gplane, const uint32_t*
                 a2k[i].y = a2k[i].y + w;
             }
         }
-#ifndef VIP_NO_SCHED_BARRIER
         __builtin_amdgcn_sched_barrier(0);
-#endif
     }
 }
 
@@ -700,7 +654,8 @@ __device__ __forceinline__ float recip_exact(float k) {
 // which q's 29 low mantissa bits show (midpoint: 2^28). Those lanes (about 2^-23 of them)
 // take the IEEE division. 7 f64 ops + 3 integer ops against the division's 11 f64 ops.
 // microbench/div_check compares it with (float)(n / d) on 2^30 inputs, half of them at
-// midpoints.
+// midpoints. The guide stage itself keeps the IEEE division (exact and measured 0.4 % slower
+// per C4 frame there); div_check is its only caller.
 __device__ __forceinline__ float rtv_quotient(double n, double d) {
     const double r0 = __builtin_amdgcn_rcp(d);
     double e = __builtin_fma(-d, r0, 1.0);

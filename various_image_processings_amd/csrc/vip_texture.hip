@@ -268,74 +268,34 @@ namespace vip {
 // round 5, per C4 frame on one stream, interleaved on one box
 // (profiles/r05_gf_tiles_{a,b,c}.txt): 92 x 36 656.1-661.0 us against 124 x 28
 // 661.7-667.2 (96 x 36 668-671, 124 x 24 673, 108 x 32 678-680, 80 x 40 697, 80 x 44 692,
-// 60 x 60 693). VIP_GF_TW / _TH / _NT override R <= 2.
+// 60 x 60 693).
 struct GfTile { int tw, th, nt; };
 // Tiles per radius for R > 2 (texture ksize 6..24; the reference's default ksize 9 is R = 4).
 // Round 6, kernel-stamped 4K launches interleaved on one box against the 64 x 16 / 256-thread
-// tile (profiles/r06_guide_tiles_big_r_ab{,2}.txt): R = 3 92 x 32 / 1024 110.7 -> 91.1 us (fewer
-// blur positions per output: 1.33 against 1.64); R = 4 the same tile with its VGPRs capped at 64
-// (two workgroups per CU, 10 spilled) 134.4 -> 110.5; R = 5 92 x 32 216.6 -> 192.3 (uncapped:
-// capped spills 37 and runs 211.5); R = 6 keeps 64 x 16 (60 x 36: 300.5, capped 261.6 against
-// 263.8); R = 7 60 x 36 capped (49 spilled) 446.7 -> 394.5. Knobs: VIP_GF_T<R> = GfTile{tw, th,
-// nt}, VIP_GF_WPE<R> = minimum waves per SIMD (8 caps the VGPRs at 64).
-#ifndef VIP_GF_T3
-#define VIP_GF_T3 GfTile{92, 32, 1024}
-#endif
-#ifndef VIP_GF_T4
-#define VIP_GF_T4 GfTile{92, 32, 1024}
-#endif
-#ifndef VIP_GF_T5
-#define VIP_GF_T5 GfTile{92, 32, 1024}
-#endif
-#ifndef VIP_GF_T6
-#define VIP_GF_T6 GfTile{64, 16, 256}
-#endif
-#ifndef VIP_GF_T7
-#define VIP_GF_T7 GfTile{60, 36, 1024}
-#endif
-#ifndef VIP_GF_WPE4
-#define VIP_GF_WPE4 8
-#endif
-#ifndef VIP_GF_WPE5
-#define VIP_GF_WPE5 1
-#endif
-#ifndef VIP_GF_WPE6
-#define VIP_GF_WPE6 1
-#endif
-#ifndef VIP_GF_WPE7
-#define VIP_GF_WPE7 8
-#endif
+// tile (profiles/r06_guide_tiles_big_r_ab{,2}.txt), per launch.
 constexpr GfTile gf_tile(int R) {
-#if defined(VIP_GF_TW) && defined(VIP_GF_TH) && defined(VIP_GF_NT)
-    if (R <= 2) return GfTile{VIP_GF_TW, VIP_GF_TH, VIP_GF_NT};
-#else
     if (R <= 2) return GfTile{92, 36, 1024};
-#endif
     switch (R) {
-        case 3: return VIP_GF_T3;
-        case 4: return VIP_GF_T4;
-        case 5: return VIP_GF_T5;
-        case 6: return VIP_GF_T6;
-        case 7: return VIP_GF_T7;
+        case 3: return GfTile{92, 32, 1024};  // 110.7 -> 91.1 us (1.33 blur positions per output against 1.64)
+        case 4: return GfTile{92, 32, 1024};  // VGPRs capped at 64 (10 spilled): 134.4 -> 110.5 us
+        case 5: return GfTile{92, 32, 1024};  // uncapped: 216.6 -> 192.3 us (capped spills 37: 211.5)
+        case 6: return GfTile{64, 16, 256};   // 60 x 36: 300.5 us, capped 261.6, against 263.8
+        case 7: return GfTile{60, 36, 1024};  // capped (49 spilled): 446.7 -> 394.5 us
         default: return GfTile{64, 16, 256};
     }
 }
-// minimum waves per SIMD the guide-stage kernel of radius R is compiled for (1: no cap)
-constexpr int gf_min_waves(int R) {
-    return R == 4 ? VIP_GF_WPE4 : R == 5 ? VIP_GF_WPE5 : R == 6 ? VIP_GF_WPE6 : R == 7 ? VIP_GF_WPE7 : 1;
-}
+// minimum waves per SIMD the guide-stage kernel of radius R is compiled for (1: no cap; 8 caps
+// the VGPRs at 64, two 1024-thread workgroups per CU: the capped tiles of gf_tile)
+constexpr int gf_min_waves(int R) { return R == 4 || R == 7 ? 8 : 1; }
 constexpr int kGfH1 = 8;   // pass 1: horizontally adjacent window aggregates per thread
 constexpr int kGfV2 = 4;   // pass 2: vertically adjacent blur positions per thread
 constexpr int kGfRun = 4;  // guide: vertically adjacent outputs per thread
 
 constexpr int cmax(int a, int b) { return a > b ? a : b; }
 
-// MRSEP_: the magnitudes get their own region beside XR (written as they are computed, no
-// barrier between pass 1 and their store), when two workgroups still fit a CU.
-template <int R, int TW_, int TH_, int NT_, bool MRSEP_ = false>
+template <int R, int TW_, int TH_, int NT_>
 struct GfGeomT {
     static constexpr int TW = TW_, TH = TH_, NT = NT_;
-    static constexpr bool MRSEP = MRSEP_;
     static_assert(TW % 4 == 0 && TH % 4 == 0, "guide tile: 4-pixel groups, 4-row runs");
     static constexpr int K = 2 * R + 1;
     static constexpr int BW = TW + 2 * R;               // BR/RR: T (+) R
@@ -351,31 +311,19 @@ struct GfGeomT {
     static constexpr int XR_WORDS = XW * XH;
     static constexpr int HPL = HWP * HH;                // one H plane
     static constexpr int BPL = BW * BHP;                // one BR/RR plane
-    // XR, then MR in its place (gradients wait in registers until XR is consumed) or, with
-    // MRSEP, beside it; H after them (RB, MX words + G as u16); BR/RR and the guide tile GT
-    // reuse it all
-    static constexpr int MR_AT = MRSEP ? XR_WORDS : 0;
-    static constexpr int H_AT = XR_WORDS + (MRSEP ? MW * MH : 0);
-    static constexpr int A_WORDS = cmax(H_AT + 2 * HPL + HPL / 2, 4 * BPL + TW * TH);
-    static constexpr int WORDS = A_WORDS;
+    // XR, then MR in its place (gradients wait in registers until XR is consumed); H after
+    // it (RB, MX words + G as u16); BR/RR and the guide tile GT reuse it all
+    static constexpr int WORDS = cmax(XR_WORDS + 2 * HPL + HPL / 2, 4 * BPL + TW * TH);
     // the exp table (64 doubles) after every region, read by the guide phase
     static constexpr int ETAB = round_up(WORDS, 4);
     static constexpr int WORDS_ALL = ETAB + 128;
-    static_assert(MRSEP || MW * MH <= XR_WORDS, "MR reuses the XR region");
+    static_assert(MW * MH <= XR_WORDS, "MR reuses the XR region");
     static constexpr int NR1 = HH * (HWP / kGfH1);      // pass-1 runs
     static constexpr int NR2 = BW * (BHP / kGfV2);      // pass-2 runs
     static constexpr int IT2 = (NR2 + NT - 1) / NT;
 };
-// Measurement knob VIP_GF_MR_SEP: MR beside XR at R = 2 (92 x 36: 80,224 bytes, still two
-// workgroups per CU), one barrier and the MR store phase fewer -- bit-exact and slower:
-// 67.8-68.3 against 65.4-65.9 us per 4K launch, interleaved (profiles/r06_guide_barrier_cuts_ab.txt)
-#ifdef VIP_GF_MR_SEP
-constexpr bool kGfMrSep2 = true;
-#else
-constexpr bool kGfMrSep2 = false;
-#endif
 template <int R>
-using GfGeom = GfGeomT<R, gf_tile(R).tw, gf_tile(R).th, gf_tile(R).nt, R == 2 && kGfMrSep2>;
+using GfGeom = GfGeomT<R, gf_tile(R).tw, gf_tile(R).th, gf_tile(R).nt>;
 
 typedef short gf_s16x2 __attribute__((ext_vector_type(2)));
 typedef unsigned short gf_u16x2 __attribute__((ext_vector_type(2)));
@@ -425,11 +373,6 @@ __device__ unsigned long long vip_gf_stamps[4096 * 16 * 16];
 // vip_stencil.hpp): band 0..3 as the thread advances through its gradients, pass-3 rows
 // and guide outputs, so the waves of a workgroup reach each phase barrier together.
 // Measured 733 -> 714 us per 4K k=5 nitr=5 frame (profiles/r02_variants.txt).
-#ifndef VIP_GF_NO_PRIO
-#define VIP_GF_PROGRESS(band) set_progress_priority(band)
-#else
-#define VIP_GF_PROGRESS(band)
-#endif
 
 // Phase 1 of a guide tile. issue() starts the global loads of the XR region of the tile with origin (x0, y0) into
 // registers (4-pixel groups, dword loads when interior and aligned, clamped bytes otherwise;
@@ -452,18 +395,7 @@ struct XrLoad {
             const int ry = g / (G::XW / 4), gx = g - ry * (G::XW / 4);
             const uint8_t* row = img + (long long)clampi(yr0 + ry, lo, hi - 1) * width * 3;
             const int x = xr0 + 4 * gx;
-#ifdef VIP_GF_ABL_LOAD  // timing ablation only (wrong output): no HBM reads
-            if (true) {
-                raw[k][0] = g * 0x01010101u;
-                raw[k][1] = (g + x) * 0x01010101u;
-                raw[k][2] = (g ^ 7) * 0x01010101u;
-            } else
-#endif
-#ifdef VIP_GF_ISA_HOT  // ISA-count builds only (scripts/isa_classes.py): the interior path alone
-            if (true) {
-#else
             if ((aligned & 1) && x >= 0 && x + 3 <= W1) {
-#endif
                 const uint32_t* w = reinterpret_cast<const uint32_t*>(row + 3 * x);
                 raw[k][0] = w[0];
                 raw[k][1] = w[1];
@@ -507,11 +439,11 @@ __device__ __forceinline__ void guide_tile(uint32_t* lds, const uint8_t* __restr
                              // uses sigma_alpha = 1/(5 ksize) even when ksize is even
     constexpr bool PACKRB = K * K * 255 < 65536;  // R|B<<16 vertical sums stay in 16 bits
     uint32_t* XR = lds;
-    uint32_t* H = lds + G::H_AT;                        // RB plane, MX plane (HPL words each)
+    uint32_t* H = lds + G::XR_WORDS;                    // RB plane, MX plane (HPL words each)
     uint16_t* HG = reinterpret_cast<uint16_t*>(H + 2 * G::HPL);  // G sums (<= K * 255) as u16
     float* BR = reinterpret_cast<float*>(lds);          // 3 planes of BPL, aliases XR/H
     float* RR = BR + 3 * G::BPL;
-    float* MR = reinterpret_cast<float*>(lds + G::MR_AT);  // (aliased: written once XR is consumed)
+    float* MR = reinterpret_cast<float*>(lds);          // aliases XR: written once XR is consumed
     double* const etab = reinterpret_cast<double*>(lds + G::ETAB);  // kExp2Tab64
     // OPAQUE_TID (the fused iteration kernel, which calls this three times): without it
     // the compiler keeps chunk 0's thread-index arithmetic live across the later chunks
@@ -532,9 +464,7 @@ __device__ __forceinline__ void guide_tile(uint32_t* lds, const uint8_t* __restr
         XrLoad<G, R> xl;
         xl.issue(img, width, lo, hi, aligned, x0, y0, tid);
         VIP_GF_STAMP(8);
-#ifndef VIP_GF_EXP_OCML
         if (tid < 64) etab[tid] = kExp2Tab64[tid];  // read in phase 4, after several barriers
-#endif
         xl.commit(XR, tid);
         VIP_GF_STAMP(1);
         __syncthreads();
@@ -545,10 +475,10 @@ __device__ __forceinline__ void guide_tile(uint32_t* lds, const uint8_t* __restr
     //     integer (< 2^24), equal to the reference's float sums: v_dot2 on the
     //     {c0, c2} 16-bit difference pairs, a mad for c1.
     constexpr int NM = G::MW * G::MH, KM = (NM + G::NT - 1) / G::NT;
-    float mrv[G::MRSEP ? 1 : KM];  // aliased MR: this thread's gradients, stored over XR after pass 1
+    float mrv[KM];  // this thread's gradients, stored over XR (MR aliases it) after pass 1
 #pragma unroll
     for (int k = 0; k < KM; ++k) {
-        VIP_GF_PROGRESS(k * 4 / KM);
+        set_progress_priority(k * 4 / KM);
         const int i = tid + k * G::NT;
         if (NM % G::NT != 0 && i >= NM) continue;
         const int qy = i / G::MW, qx = i - qy * G::MW;
@@ -561,15 +491,7 @@ __device__ __forceinline__ void guide_tile(uint32_t* lds, const uint8_t* __restr
         const int v1 = (int)__builtin_amdgcn_ubfe(D, 8, 8) - (int)__builtin_amdgcn_ubfe(U, 8, 8);
         const int ss = __builtin_amdgcn_sdot2(h02, h02, __builtin_amdgcn_sdot2(v02, v02, h1 * h1 + v1 * v1, false),
                                               false);
-#ifdef VIP_GF_LLVM_SQRT  // the compiler's correctly rounded expansion (same result, 17 VALU)
-        const float mag = __builtin_sqrtf((float)ss);
-#else
-        const float mag = sqrt_int_exact((float)ss);  // == sqrtf, exhaustively checked (microbench/div_check)
-#endif
-        if constexpr (G::MRSEP)
-            MR[i] = mag;
-        else
-            mrv[k] = mag;
+        mrv[k] = sqrt_int_exact((float)ss);  // == sqrtf, exhaustively checked (microbench/div_check)
     }
     VIP_GF_STAMP(9);
     // 2b. pass 1: H = horizontal K-window aggregates, kGfH1 adjacent columns per thread.
@@ -604,17 +526,15 @@ __device__ __forceinline__ void guide_tile(uint32_t* lds, const uint8_t* __restr
     }
     VIP_GF_STAMP(2);
     __syncthreads();  // XR is consumed (gradients and pass 1): MR takes its place
-    if constexpr (!G::MRSEP) {
-        VIP_GF_PROGRESS(0);
+    set_progress_priority(0);
 #pragma unroll
-        for (int k = 0; k < KM; ++k) {
-            const int i = tid + k * G::NT;
-            if (NM % G::NT != 0 && i >= NM) continue;
-            MR[i] = mrv[k];
-        }
-        VIP_GF_STAMP(3);
-        __syncthreads();
+    for (int k = 0; k < KM; ++k) {
+        const int i = tid + k * G::NT;
+        if (NM % G::NT != 0 && i >= NM) continue;
+        MR[i] = mrv[k];
     }
+    VIP_GF_STAMP(3);
+    __syncthreads();
 
     // 3. pass 2: blur + mRTV at the BR positions, kGfV2 vertically adjacent positions per
     //    thread (vertical windows of H, magnitude sums in row-major order). Blur
@@ -622,14 +542,7 @@ __device__ __forceinline__ void guide_tile(uint32_t* lds, const uint8_t* __restr
     //    MR rows p .. p + 2R, columns c .. c + 2R. Results stay in registers until every
     //    thread is done with H (BR/RR alias it).
     const float kk = (float)(ksize * ksize);
-    // == 1.f / kk (RN(1/k) for every float k in [1, 2^38), microbench/div_check), 3 VALU
-    // instead of the IEEE division's ~10
-#ifndef VIP_GF_FAST_DIV
     const float rkk = 1.f / kk;
-#else  // measurement knob, same values: 3 VALU instead of the IEEE division's ~10, but the
-       // C4 frame measured 0.4 % slower with it and rtv_quotient (profiles/r04_gf_fast_div.txt)
-    const float rkk = recip_exact(kk);
-#endif
     constexpr float kThird = 0x1.555556p-2f;  // RN(1/3)
     float res[G::IT2][kGfV2][4];
 #pragma unroll
@@ -640,11 +553,7 @@ __device__ __forceinline__ void guide_tile(uint32_t* lds, const uint8_t* __restr
         const int ix = x0 - R + c, iy0 = y0 - R + p0;
         uint32_t s0[kGfV2], s1[kGfV2], s2[kGfV2], smx[kGfV2];
         float mmax[kGfV2], msum[kGfV2];
-#ifdef VIP_GF_ISA_HOT
-        if (true) {
-#else
         if (ix >= 0 && ix <= W1 && iy0 >= H0 && iy0 + kGfV2 - 1 <= H1) {
-#endif
             constexpr int NV = kGfV2 + K - 1;
             uint32_t hrb[NV], hg[NV], hmx[NV];
             // magnitudes are finite and >= +0: their bit patterns order like their values, so
@@ -672,7 +581,7 @@ __device__ __forceinline__ void guide_tile(uint32_t* lds, const uint8_t* __restr
             win_op<kGfV2, K>(hmx, smx, pk_max_u16);
 #pragma unroll
             for (int t = 0; t < NV; ++t) {
-                VIP_GF_PROGRESS(t * 4 / NV);
+                set_progress_priority(t * 4 / NV);
                 const float* mrow = MR + (p0 + t) * G::MW + c;
                 float m[K];
 #pragma unroll
@@ -742,15 +651,7 @@ __device__ __forceinline__ void guide_tile(uint32_t* lds, const uint8_t* __restr
             const float imax = div_exact(smx[j] & 0xffffu, 3.f, kThird);
             const float imin = div_exact(1023u - (smx[j] >> 16), 3.f, kThird);
             const float num = (imax - imin) * mmax[j];
-#ifdef VIP_GF_ABL_DIV  // timing ablation only (inexact): f32 divide instead of the double one
-            res[it][j][3] = num / (msum[j] + 1e-9f);
-#else
-#ifndef VIP_GF_FAST_DIV
             res[it][j][3] = CPP ? num / (msum[j] + 1e-9f) : (float)((double)num / ((double)msum[j] + 1e-9));
-#else
-            res[it][j][3] = CPP ? num / (msum[j] + 1e-9f) : rtv_quotient((double)num, (double)msum[j] + 1e-9);
-#endif
-#endif
         }
     }
     VIP_GF_STAMP(4);
@@ -777,25 +678,18 @@ __device__ __forceinline__ void guide_tile(uint32_t* lds, const uint8_t* __restr
     //    takes kGfRun vertically adjacent outputs: each window row's first argmin is
     //    found once and shared; scanning those rows in order with strict > then
     //    gives the row-major first argmin. Alpha blend per output.
-#ifndef VIP_GF_FAST_DIV
     const float sigma_alpha = 1.f / (float)(5 * ksize);
-#else
-    const float sigma_alpha = recip_exact((float)(5 * ksize));  // == 1.f / (5 ksize), as rkk
-#endif
     for (int run = tid; run < (G::TH / kGfRun) * G::TW; run += G::NT) {
         const int tx = run % G::TW, ty0 = (run / G::TW) * kGfRun;
         const int x = x0 + tx;
         if (x > W1 || y0 + ty0 >= gy1) continue;
-#ifndef VIP_GF_ARGMIN_SCAN
         // rtv is finite and >= +0 (num >= 0, msum + 1e-9 > 0), so its bit patterns order
         // like its values: each row's minimum is an integer min3 (no NaN canonicalising),
         // its first position the lowest column holding that minimum -- the same position
         // as the reference's strict > scan. Every rtv is <= 255 < the scan's initial 1e10f
         // (FLT_MAX in the CPP profile), so that initial value never survives.
         uint32_t rv[kGfRun + 2 * R];
-#ifndef VIP_GF_ARGMIN_LATE
         int ri[kGfRun + 2 * R];
-#endif
 #pragma unroll
         for (int t = 0; t < kGfRun + 2 * R; ++t) {  // window rows ty0-R .. ty0+kGfRun-1+R
             const float* row = RR + (ty0 + t) * G::BW + tx;
@@ -806,83 +700,28 @@ __device__ __forceinline__ void guide_tile(uint32_t* lds, const uint8_t* __restr
 #pragma unroll
             for (int kx = 1; kx < K; ++kx) v = v < m[kx] ? v : m[kx];
             rv[t] = v;
-#ifndef VIP_GF_ARGMIN_LATE
             int c = K - 1;
 #pragma unroll
             for (int kx = K - 2; kx >= 0; --kx) c = m[kx] == v ? kx : c;
             ri[t] = (ty0 + t) * G::BW + tx + c;
-#endif
         }
 #pragma unroll
         for (int j = 0; j < kGfRun; ++j) {
-            VIP_GF_PROGRESS(j * 4 / kGfRun);
+            set_progress_priority(j * 4 / kGfRun);
             const int y = y0 + ty0 + j;
             if (y >= gy1) break;
             uint32_t mb = rv[j];
 #pragma unroll
             for (int ky = 1; ky < K; ++ky) mb = mb < rv[j + ky] ? mb : rv[j + ky];
-#ifndef VIP_GF_ARGMIN_LATE
             int mi = ri[j + K - 1];
 #pragma unroll
             for (int ky = K - 2; ky >= 0; --ky) mi = rv[j + ky] == mb ? ri[j + ky] : mi;
-#else  // measurement knob: row minima only; the argmin's row, then its column, per output
-            int roff = (j + K - 1) * G::BW;
-#pragma unroll
-            for (int ky = K - 2; ky >= 0; --ky) roff = rv[j + ky] == mb ? (j + ky) * G::BW : roff;
-            const int rowi = ty0 * G::BW + tx + roff;
-            uint32_t mm[K];
-#pragma unroll
-            for (int kx = 0; kx < K; ++kx) mm[kx] = __float_as_uint(RR[rowi + kx]);
-            int c = K - 1;
-#pragma unroll
-            for (int kx = K - 2; kx >= 0; --kx) c = mm[kx] == mb ? kx : c;
-            const int mi = rowi + c;
-#endif
             const float rmin = __uint_as_float(mb);
-#else  // the reference's scan: compare and select per position
-        float rv[kGfRun + 2 * R];
-        int ri[kGfRun + 2 * R];
-#pragma unroll
-        for (int t = 0; t < kGfRun + 2 * R; ++t) {  // window rows ty0-R .. ty0+kGfRun-1+R
-            const float* row = RR + (ty0 + t) * G::BW + tx;
-            float v = row[0];
-            int c = 0;
-#pragma unroll
-            for (int kx = 1; kx < K; ++kx) {
-                if (v > row[kx]) {
-                    v = row[kx];
-                    c = kx;
-                }
-            }
-            rv[t] = v;
-            ri[t] = (ty0 + t) * G::BW + tx + c;
-        }
-#pragma unroll
-        for (int j = 0; j < kGfRun; ++j) {
-            VIP_GF_PROGRESS(j * 4 / kGfRun);
-            const int y = y0 + ty0 + j;
-            if (y >= gy1) break;
-            float rmin = CPP ? 3.402823466e+38f : 1e10f;
-            int mi = 0;
-#pragma unroll
-            for (int ky = 0; ky < K; ++ky) {
-                if (rmin > rv[j + ky]) {
-                    rmin = rv[j + ky];
-                    mi = ri[j + ky];
-                }
-            }
-#endif
             const int ci = (ty0 + j + R) * G::BW + tx + R;
             const float arg = sigma_alpha * (RR[ci] - rmin);
-#ifdef VIP_GF_ABL_EXP  // timing ablation only (inexact): hardware exp2
-            const float e = __builtin_amdgcn_exp2f(arg * 1.44269504f);
-#elif defined(VIP_GF_EXP_OCML)  // ocml's double exp
-            const float e = (float)exp((double)arg);
-#else
             // == (float)exp((double)arg) for every float arg in [0, 32) (microbench/div_check
             // on the GPU; microbench/exp_check against glibc, the oracle's exp)
             const float e = exp_tab_f32(arg, etab);
-#endif
             // 2 / (1 + e) == 2 * RN(1 / (1 + e)) exactly (a power-of-two scale). e >= 1 and
             // arg <= 255 / (5 ksize) (rtv <= 255): 1 + e < 2^17 for ksize >= 5, < 2^37 at
             // ksize 2 (ksize 1: arg = 0). microbench/div_check verifies recip_exact for every
@@ -941,32 +780,8 @@ void texture_guide_fused_kernel(const uint8_t* __restrict__ img,
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     const int x0 = blockIdx.x * G::TW, y0 = gy0 + blockIdx.y * G::TH;
     const int tid = threadIdx.x;
-    const int W1 = width - 1;
     VIP_GF_STAMP(0);
-#ifdef VIP_GF_DIRECT_STORE
-    // measurement knob: guide words straight to HBM -- a quad of lanes holds 4 horizontally
-    // adjacent pixels (the guide runs are column-major in the lanes, TW % 4 == 0), lanes 0-2
-    // of the quad store one dword each of the 12 bytes; byte stores at a ragged edge or an
-    // unaligned buffer. No guide tile in LDS and no barrier after the guide phase; bit-exact
-    // and 1 us slower per launch on top of VIP_GF_MR_SEP (profiles/r06_guide_barrier_cuts_ab.txt).
-    static_assert(G::TW % 4 == 0, "whole quads per guide row");
-    guide_tile<G, R, CPP>(lds, img, width, lo, hi, gy1, ksize, aligned, x0, y0, [&](int ty, int tx, uint32_t gw) {
-        const uint32_t nx = (uint32_t)__builtin_amdgcn_mov_dpp((int)gw, 0xF9, 0xF, 0xF, false);  // quad_perm 1,2,3,3
-        const int q = tx & 3, xq = x0 + tx - q;
-        uint8_t* const orow = guide + ((long long)(y0 + ty) * width + xq) * 3;
-        if ((aligned & 2) && xq + 3 <= W1) {
-            if (q < 3) reinterpret_cast<uint32_t*>(orow)[q] = (gw >> (8 * q)) | (nx << (24 - 8 * q));
-        } else {
-            uint8_t* const o = orow + 3 * q;
-            o[0] = (uint8_t)gw;
-            o[1] = (uint8_t)(gw >> 8);
-            o[2] = (uint8_t)(gw >> 16);
-        }
-    });
-    (void)tid;
-    VIP_GF_STAMP(6);
-    VIP_GF_STAMP(7);
-#else  // the guide tile through LDS, one barrier, then dword rows
+    // the guide tile through LDS, one barrier, then dword rows
     uint32_t* GT = lds + 4 * G::BPL;  // guide tile as RGBX words, after BR/RR
     guide_tile<G, R, CPP>(lds, img, width, lo, hi, gy1, ksize, aligned, x0, y0,
                           [&](int ty, int tx, uint32_t gw) { GT[ty * G::TW + tx] = gw; });
@@ -975,7 +790,6 @@ void texture_guide_fused_kernel(const uint8_t* __restrict__ img,
 
     store_guide_tile<G>(GT, guide, width, x0, y0, gy1, aligned, tid);
     VIP_GF_STAMP(7);
-#endif
 }
 
 template <int R, bool CPP>
@@ -994,358 +808,9 @@ static int launch_gf(const uint8_t* img, uint8_t* guide, int width, int lo, int 
     return (int)hipGetLastError();
 }
 
-// ---------------------------------------------------------------------------
-// Streaming guide stage, R = 2 (ksize 4 and 5: C4) -- built, bit-exact, and SLOWER: 90.1
-// against 65.0 us per 4K launch (profiles/r06_guide_stage_ab.txt), so it is a build knob
-// (VIP_GF_STREAM), not the default. The rings cost 52 KiB per 512-thread workgroup, so only
-// two workgroups share a CU at its 121 VGPRs (three at 80 VGPRs spill: 126.8 us); the guide
-// and pass-2 phases then run on 2 of a SIMD's 4 waves, where the tiled stage runs each phase
-// on all 8 -- the phases' LDS and f64 latency chains are no longer hidden. Same arithmetic
-// as guide_tile, same bytes; a different schedule. One workgroup walks down a strip of GsTW output columns over
-// a segment of rows, kGsV rows per step, and every phase of the stage is in flight in every
-// step, each on its own row group (a software pipeline with one barrier per step):
-//   A  image rows [Y0 + 5 + sV, +V): global loads issued at the top of step s, written to the
-//      XR ring at its end (the loads fly under the step's compute)
-//   B  rows [Y0 + 4 + (s-1)V, +V): gradient magnitudes (MR ring) and the horizontal K-window
-//      aggregates of pass 1 (H ring), from XR rows stored by step s - 1
-//   C  rows [Y0 + 2 + (s-2)V, +V): pass 2, box blur + mRTV (BR/RR rings), from H/MR rows of
-//      step s - 1 (vertical windows of H, magnitude sums in the reference's row-major order)
-//   D  rows [Y0 + (s-3)V, +V): the guide (first strict argmin, alpha blend) from BR/RR rows
-//      of step s - 1, straight to HBM (a quad of lanes assembles 4 RGB pixels into 3 dwords)
-// Each stage lags the one it reads by exactly the rows it needs (V + 1 rows for B, V + R for
-// C and D), so one step of lag suffices and the rings hold 10 (XR) and 12 rows (the rest).
-// The vertical apron is paid once per segment instead of once per tile: 1.03 blur positions
-// and 1.06 gradients per output against the tiled stage's 1.16 and 1.33. The waves take
-// roles: 0-1 the guide, 2-3 pass 2, 4-6 gradients and loads, 7 pass 1 -- two heavy and one
-// or two light waves per SIMD, so no SIMD idles while a phase of another runs alone.
-// Rings hold only rows in [lo, hi) (slot = row mod ring size); every reader clamps its row
-// index, as the reference clamps its coordinates. Columns stay pre-clamped (XR holds the
-// pixel at the clamped column, so MR, H and BR/RR hold the values at clamped centres).
-// ---------------------------------------------------------------------------
-namespace gs {
-constexpr int R = 2, K = 2 * R + 1, V = 4;
-constexpr int TW = 124, NT = 512;        // output columns per strip; 8 waves
-constexpr int BW = TW + 2 * R;           // 128 blur / H columns: image x0 - R + c
-constexpr int MW = TW + 4 * R;           // 132 magnitude columns: image x0 - 2R + c
-constexpr int XL = 8;                    // XR column 0 = image x0 - XL (4-pixel aligned)
-constexpr int XG = 35, XW = 4 * XG;      // 140 XR words per row: image x0 - 8 .. x0 + 131
-constexpr int XRING = 10, RING = 12;     // ring rows
-constexpr int O_XR = 0;
-constexpr int O_MR = O_XR + XRING * XW;
-constexpr int O_HRB = O_MR + RING * MW;  // R | B << 16 window sums
-constexpr int O_HMX = O_HRB + RING * BW; // max s | (1023 - min s) << 16, s = r + g + b
-constexpr int O_HG = O_HMX + RING * BW;  // G window sums, u16
-constexpr int O_BR = O_HG + RING * BW / 2;
-constexpr int O_RR = O_BR + 3 * RING * BW;
-constexpr int O_ET = round_up(O_RR + RING * BW, 2);
-constexpr int WORDS = O_ET + 128;        // + the exp table (64 doubles)
-constexpr int LDS = 4 * WORDS;           // 52,384 bytes: three workgroups per CU
-constexpr int NGRAD = V * MW;            // 528 gradients per step (waves 4-6, <= 3 each)
-constexpr int NLOAD = V * XG;            // 140 four-pixel loads per step (waves 4-6)
-static_assert(TW % 4 == 0 && TW <= 128 && BW == 128, "guide on waves 0-1, pass 2 on waves 2-3");
-static_assert(V * (BW / 8) == 64, "pass 1 on wave 7: one run of 8 columns per lane");
-static_assert(NGRAD <= 3 * 192 && NLOAD <= 192, "gradients and loads on waves 4-6");
-static_assert(XW - XL >= TW + 2 * R + 2 && XW % 4 == 0, "XR covers the gradient and pass-1 reads");
-static_assert(3 * LDS <= kLdsBudget, "three workgroups per CU");
-constexpr int kMinSegRows = 16;          // rows per segment at least (the apron is ~10 rows)
-}  // namespace gs
-
-#ifdef VIP_GS_WAVES_PER_EU  // measurement knob: cap the VGPRs so more workgroups share a CU
-#define VIP_GS_OCC __attribute__((amdgpu_waves_per_eu(VIP_GS_WAVES_PER_EU, VIP_GS_WAVES_PER_EU)))
-#else
-#define VIP_GS_OCC
-#endif
-template <bool CPP>
-__global__ __launch_bounds__(gs::NT) VIP_GS_OCC void texture_guide_stream_kernel(const uint8_t* __restrict__ img,
-                                                                      uint8_t* __restrict__ guide, int width, int lo,
-                                                                      int hi, int gy0, int gy1, int seg_rows,
-                                                                      int ksize, int aligned) {
-    using namespace gs;
-    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
-    uint32_t* const XR = lds + O_XR;
-    float* const MR = reinterpret_cast<float*>(lds + O_MR);
-    uint32_t* const HRB = lds + O_HRB;
-    uint32_t* const HMX = lds + O_HMX;
-    uint16_t* const HG = reinterpret_cast<uint16_t*>(lds + O_HG);
-    float* const BR = reinterpret_cast<float*>(lds + O_BR);  // 3 planes of RING x BW
-    float* const RR = reinterpret_cast<float*>(lds + O_RR);
-    double* const etab = reinterpret_cast<double*>(lds + O_ET);
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int x0 = blockIdx.x * TW, xr0 = x0 - XL;
-    const int Y0 = gy0 + blockIdx.y * seg_rows;
-    const int Y1 = Y0 + seg_rows < gy1 ? Y0 + seg_rows : gy1;
-    if (Y0 >= Y1) return;  // whole workgroup
-    const int W1 = width - 1, H1 = hi - 1;
-    // rows each stage produces (the guide rows' reach, clamped to the valid rows)
-    const int as = Y0 - 2 * R - 1 > lo ? Y0 - 2 * R - 1 : lo, ae = Y1 + 2 * R + 1 < hi ? Y1 + 2 * R + 1 : hi;
-    const int bs = Y0 - 2 * R > lo ? Y0 - 2 * R : lo, be = Y1 + 2 * R < hi ? Y1 + 2 * R : hi;
-    const int cs = Y0 - R > lo ? Y0 - R : lo, ce = Y1 + R < hi ? Y1 + R : hi;
-    if (tid < 64) etab[tid] = kExp2Tab64[tid];  // first read by D at step 3, after barriers
-    const float kk = (float)(ksize * ksize);
-    const float rkk = 1.f / kk;
-    constexpr float kThird = 0x1.555556p-2f;  // RN(1/3)
-    const float sigma_alpha = 1.f / (float)(5 * ksize);
-    const int ngroups = (Y1 - Y0 + V - 1) / V;
-
-    for (int s = -3; s < ngroups + 3; ++s) {
-        // ---- A: issue this step's image loads (waves 4-6) ----
-        uint32_t raw0 = 0, raw1 = 0, raw2 = 0;
-        int xr_at = -1;  // XR word the loaded group goes to
-        if (wave >= 4 && wave < 7) {
-            const int i = tid - 256;
-            if (i < NLOAD) {
-                const int rr = i / XG, gx = i - rr * XG;
-                const int r = Y0 + 2 * R + 1 + s * V + rr;
-                if (r >= as && r < ae) {
-                    const uint8_t* row = img + (long long)r * width * 3;
-                    const int x = xr0 + 4 * gx;
-                    if ((aligned & 1) && x >= 0 && x + 3 <= W1) {
-                        const uint32_t* w = reinterpret_cast<const uint32_t*>(row + 3 * x);
-                        raw0 = w[0];
-                        raw1 = w[1];
-                        raw2 = w[2];
-                    } else {
-                        const uint32_t q0 = load_rgb(row, clampi(x, 0, W1)), q1 = load_rgb(row, clampi(x + 1, 0, W1));
-                        const uint32_t q2 = load_rgb(row, clampi(x + 2, 0, W1)), q3 = load_rgb(row, clampi(x + 3, 0, W1));
-                        raw0 = q0 | (q1 << 24);
-                        raw1 = (q1 >> 8) | (q2 << 16);
-                        raw2 = (q2 >> 16) | (q3 << 8);
-                    }
-                    xr_at = (r % XRING) * XW + 4 * gx;
-                }
-            }
-        }
-
-        if (wave < 2) {
-            // ---- D: guide rows [g0, g0 + V) ----
-            const int g0 = Y0 + (s - 3) * V;
-            if (s >= 3) {
-                const int tx = lane + 64 * wave;
-                const int txr = tx < TW ? tx : TW - 1;  // lanes past the strip read in-strip values
-                // window rows g0 - R .. g0 + V - 1 + R (clamped): each row's minimum and the
-                // first column holding it (rtv >= +0 and finite: bit patterns order like values)
-                uint32_t rv[V + 2 * R];
-                int ri[V + 2 * R];
-#pragma unroll
-                for (int t = 0; t < V + 2 * R; ++t) {
-                    const int row = clampi(g0 - R + t, lo, H1);
-                    const int base = (row % RING) * BW + txr;
-                    uint32_t m[K];
-#pragma unroll
-                    for (int kx = 0; kx < K; ++kx) m[kx] = __float_as_uint(RR[base + kx]);
-                    uint32_t v = m[0];
-#pragma unroll
-                    for (int kx = 1; kx < K; ++kx) v = v < m[kx] ? v : m[kx];
-                    rv[t] = v;
-                    int c = K - 1;
-#pragma unroll
-                    for (int kx = K - 2; kx >= 0; --kx) c = m[kx] == v ? kx : c;
-                    ri[t] = base + c;
-                }
-                const int x = x0 + tx;
-                const int q = lane & 3;
-                // a quad of lanes = 4 pixels = 3 dwords (lanes 0-2 store one each); whole
-                // quads are in or out of the strip (TW % 4 == 0)
-                const bool dword_quad = (aligned & 2) && tx - q + 3 < TW && x - q + 3 <= W1;
-#pragma unroll
-                for (int j = 0; j < V; ++j) {
-                    const int g = g0 + j;
-                    if (g >= Y1) break;
-                    uint32_t mb = rv[j];
-#pragma unroll
-                    for (int ky = 1; ky < K; ++ky) mb = mb < rv[j + ky] ? mb : rv[j + ky];
-                    int mi = ri[j + K - 1];
-#pragma unroll
-                    for (int ky = K - 2; ky >= 0; --ky) mi = rv[j + ky] == mb ? ri[j + ky] : mi;
-                    const float rmin = __uint_as_float(mb);
-                    const int ci = (g % RING) * BW + txr + R;
-                    const float arg = sigma_alpha * (RR[ci] - rmin);
-                    const float e = exp_tab_f32(arg, etab);  // == (float)exp((double)arg)
-                    const float alpha = 2.f * recip_exact(1.f + e) - 1.f;
-                    const float beta = 1.f - alpha;
-                    uint32_t gw = 0;
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) {
-                        const float bm = BR[c * RING * BW + mi], bc = BR[c * RING * BW + ci];
-                        const float v = CPP ? (alpha * bm + beta * bc) + 0.5f : __builtin_fmaf(alpha, bm, beta * bc) + 0.5f;
-                        gw = pack_u8_clamped(v, c, gw);  // == clampi((int)v, 0, 255) << 8c
-                    }
-                    // the next lane's pixel (quad_perm [1, 2, 3, 3])
-                    const uint32_t nx = (uint32_t)__builtin_amdgcn_mov_dpp((int)gw, 0xF9, 0xF, 0xF, false);
-                    uint8_t* const orow = guide + ((long long)g * width + (x - q)) * 3;
-                    if (dword_quad) {
-                        if (q < 3)
-                            reinterpret_cast<uint32_t*>(orow)[q] = (gw >> (8 * q)) | (nx << (24 - 8 * q));
-                    } else if (tx < TW && x <= W1) {
-                        uint8_t* const o = orow + 3 * q;
-                        o[0] = (uint8_t)gw;
-                        o[1] = (uint8_t)(gw >> 8);
-                        o[2] = (uint8_t)(gw >> 16);
-                    }
-                }
-            }
-        } else if (wave < 4) {
-            // ---- C: pass 2 at blur rows [p0, p0 + V), column bc ----
-            const int p0 = Y0 + R + (s - 2) * V;
-            if (p0 + V > cs && p0 < ce) {
-                const int bc = tid - 128;
-                // the blur centre's clamped column: its H column and its MR window's first column
-                const int hcol = clampi(x0 - R + bc, 0, W1) - (x0 - R);
-                constexpr int NV = V + K - 1;
-                uint32_t hrb[NV], hg[NV], hmx[NV], rowmax[NV];
-                int hro[NV];
-#pragma unroll
-                for (int t = 0; t < NV; ++t) {
-                    hro[t] = clampi(p0 - R + t, lo, H1) % RING;
-                    hrb[t] = HRB[hro[t] * BW + hcol];
-                    hg[t] = HG[hro[t] * BW + hcol];
-                    hmx[t] = HMX[hro[t] * BW + hcol];
-                }
-                uint32_t s0[V], s1[V], smx[V], mmaxb[V];
-                float msum[V];
-                win_sum<V, K>(hrb, s0);
-                win_sum<V, K>(hg, s1);
-                win_op<V, K>(hmx, smx, pk_max_u16);
-#pragma unroll
-                for (int t = 0; t < NV; ++t) {
-                    const float* mrow = MR + hro[t] * MW + hcol;
-                    float m[K];
-#pragma unroll
-                    for (int kx = 0; kx < K; ++kx) m[kx] = mrow[kx];
-                    uint32_t mx = __float_as_uint(m[0]);
-#pragma unroll
-                    for (int kx = 1; kx < K; ++kx) {  // == the reference's max (no NaN, >= +0)
-                        const uint32_t b = __float_as_uint(m[kx]);
-                        mx = mx > b ? mx : b;
-                    }
-                    rowmax[t] = mx;
-#pragma unroll
-                    for (int j = 0; j < V; ++j) {  // window row t - j of position j, row-major
-                        if (t - j < 0 || t - j >= K) continue;
-                        msum[j] = t == j ? m[0] : msum[j] + m[0];
-#pragma unroll
-                        for (int kx = 1; kx < K; ++kx) msum[j] = msum[j] + m[kx];
-                    }
-                }
-                win_op<V, K>(rowmax, mmaxb, [](uint32_t a, uint32_t b) { return a > b ? a : b; });
-#pragma unroll
-                for (int j = 0; j < V; ++j) {
-                    const int p = p0 + j;
-                    if (p < cs || p >= ce) continue;
-                    const int o = (p % RING) * BW + bc;
-                    BR[o] = div_exact(s0[j] & 0xffffu, kk, rkk);
-                    BR[RING * BW + o] = div_exact(s1[j], kk, rkk);
-                    BR[2 * RING * BW + o] = div_exact(s0[j] >> 16, kk, rkk);
-                    const float imax = div_exact(smx[j] & 0xffffu, 3.f, kThird);
-                    const float imin = div_exact(1023u - (smx[j] >> 16), 3.f, kThird);
-                    const float num = (imax - imin) * __uint_as_float(mmaxb[j]);
-                    RR[o] = CPP ? num / (msum[j] + 1e-9f) : (float)((double)num / ((double)msum[j] + 1e-9));
-                }
-            }
-        } else {
-            const int b0 = Y0 + 2 * R + (s - 1) * V;
-            if (b0 + V > bs && b0 < be) {
-                if (wave < 7) {
-                    // ---- B: gradient magnitudes at rows [b0, b0 + V), MR columns ----
-#pragma unroll
-                    for (int k = 0; k < 3; ++k) {
-                        const int i = tid - 256 + k * 192;
-                        if (i >= NGRAD) break;
-                        const int rr = i / MW, mc = i - rr * MW;
-                        const int r = b0 + rr;
-                        if (r < bs || r >= be) continue;
-                        const int cx = clampi(x0 - 2 * R + mc, 0, W1) - xr0;
-                        const uint32_t* rc = XR + (r % XRING) * XW + cx;
-                        const uint32_t U = XR[((r - 1 > lo ? r - 1 : lo) % XRING) * XW + cx];
-                        const uint32_t D = XR[((r + 1 < H1 ? r + 1 : H1) % XRING) * XW + cx];
-                        const uint32_t L = rc[-1], Rt = rc[1];
-                        const gf_s16x2 h02 = __builtin_bit_cast(gf_s16x2, Rt & 0x00ff00ffu) -
-                                             __builtin_bit_cast(gf_s16x2, L & 0x00ff00ffu);
-                        const gf_s16x2 v02 = __builtin_bit_cast(gf_s16x2, D & 0x00ff00ffu) -
-                                             __builtin_bit_cast(gf_s16x2, U & 0x00ff00ffu);
-                        const int h1 = (int)__builtin_amdgcn_ubfe(Rt, 8, 8) - (int)__builtin_amdgcn_ubfe(L, 8, 8);
-                        const int v1 = (int)__builtin_amdgcn_ubfe(D, 8, 8) - (int)__builtin_amdgcn_ubfe(U, 8, 8);
-                        const int ss = __builtin_amdgcn_sdot2(
-                            h02, h02, __builtin_amdgcn_sdot2(v02, v02, h1 * h1 + v1 * v1, false), false);
-                        MR[(r % RING) * MW + mc] = sqrt_int_exact((float)ss);  // == sqrtf
-                    }
-                } else {
-                    // ---- B: pass 1, H at row b0 + lane / 16, columns 8 (lane % 16) .. +8 ----
-                    const int r = b0 + (lane >> 4), hc0 = (lane & 15) * 8;
-                    if (r >= bs && r < be) {
-                        const uint32_t* xrow = XR + (r % XRING) * XW + hc0 + XL - 2 * R;
-                        constexpr int NX = 8 + K - 1;
-                        uint32_t rb[NX], gg[NX], mx[NX];
-#pragma unroll
-                        for (int t = 0; t < NX; ++t) {
-                            const uint32_t p = xrow[t];
-                            const uint32_t sb = __builtin_amdgcn_sad_u8(p, 0u, 0u);  // r + g + b
-                            rb[t] = p & 0x00ff00ffu;
-                            gg[t] = __builtin_amdgcn_ubfe(p, 8, 8);
-                            mx[t] = ((sb ^ 1023u) << 16) | sb;  // max of lo = max s, of hi = 1023 - min s
-                        }
-                        uint32_t orb[8], og[8], omx[8];
-                        win_sum<8, K>(rb, orb);
-                        win_sum<8, K>(gg, og);
-                        win_op<8, K>(mx, omx, pk_max_u16);
-                        const int o = (r % RING) * BW + hc0;
-                        *reinterpret_cast<uint4*>(HG + o) = make_uint4(og[0] | (og[1] << 16), og[2] | (og[3] << 16),
-                                                                       og[4] | (og[5] << 16), og[6] | (og[7] << 16));
-#pragma unroll
-                        for (int j = 0; j < 8; j += 4) {
-                            *reinterpret_cast<uint4*>(HRB + o + j) = make_uint4(orb[j], orb[j + 1], orb[j + 2], orb[j + 3]);
-                            *reinterpret_cast<uint4*>(HMX + o + j) = make_uint4(omx[j], omx[j + 1], omx[j + 2], omx[j + 3]);
-                        }
-                    }
-                }
-            }
-        }
-        // ---- A: the loaded image group into the XR ring ----
-        if (xr_at >= 0) *reinterpret_cast<uint4*>(XR + xr_at) = unpack_rgb4(raw0, raw1, raw2);
-        __syncthreads();
-    }
-}
-
-// Segments per strip: as many as fill the workgroup slots of the device in one round (the
-// runtime's occupancy for this kernel: LDS and VGPRs), each at least kMinSegRows rows (the
-// pipeline's apron is about ten rows).
-template <bool CPP>
-static int launch_gs(const uint8_t* img, uint8_t* guide, int width, int lo, int hi, int gy0, int gy1, int ksize,
-                     int aligned, hipStream_t stream) {
-    auto kern = texture_guide_stream_kernel<CPP>;
-    static std::atomic<unsigned long long> attr_devs{0};
-    if (const int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), gs::LDS, attr_devs)) return rc;
-    note_launch(reinterpret_cast<const void*>(kern));
-    if (gy1 <= gy0) return 0;
-    static std::atomic<int> per_cu{0};  // workgroups per CU (the same on every MI355X)
-    int wg = per_cu.load(std::memory_order_relaxed);
-    if (wg == 0) {
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&wg, reinterpret_cast<const void*>(kern), gs::NT, gs::LDS) !=
-                hipSuccess ||
-            wg < 1)
-            wg = 1;
-        per_cu.store(wg, std::memory_order_relaxed);
-    }
-    const int rows = gy1 - gy0;
-    const int strips = (width + gs::TW - 1) / gs::TW;
-    const int slots = wg * device_cus();
-    int nseg = slots / strips;
-    const int max_seg = (rows + gs::kMinSegRows - 1) / gs::kMinSegRows;
-    nseg = nseg < 1 ? 1 : (nseg > max_seg ? max_seg : nseg);
-    const int seg_rows = (rows + nseg - 1) / nseg;
-    nseg = (rows + seg_rows - 1) / seg_rows;
-    launch(kern, dim3(strips, nseg), dim3(gs::NT), gs::LDS, stream, img, guide, width, lo, hi, gy0, gy1, seg_rows,
-           ksize, aligned);
-    return (int)hipGetLastError();
-}
-
 template <bool CPP>
 static int launch_gf_r(int ksize, const uint8_t* img, uint8_t* guide, int width, int lo, int hi, int gy0, int gy1,
                        int aligned, hipStream_t s) {
-#ifdef VIP_GF_STREAM  // measurement knob: the streaming stage at R = 2 (bit-exact, 1.39x slower)
-    if (ksize / 2 == 2) return launch_gs<CPP>(img, guide, width, lo, hi, gy0, gy1, ksize, aligned, s);
-#endif
 #ifdef VIP_GF_ONLY_R2  // quick variant builds (scripts/build_texture_variant.sh): k = 4, 5 only
     if (ksize / 2 == 2) return launch_gf<2, CPP>(img, guide, width, lo, hi, gy0, gy1, ksize, aligned, s);
     return VIP_ERR_UNSUPPORTED_KSIZE;
@@ -1492,8 +957,8 @@ __global__ __launch_bounds__(kFuNT) void texture_iteration_fused_kernel(const St
             const uint32_t d = __builtin_amdgcn_sad_u8(g, ctr[i], 0u);
             return (d << 6) | lane4;  // 16 copies: word d * 16 + copy
         };
-        row_taps<HW, FuJG::L, C0, NC, FMA, false, P, true, decltype(widx)&>(gplane, splane, row_off, wsv, lut_bytes,
-                                                                            widx, a01, a2k);
+        row_taps<HW, FuJG::L, C0, NC, FMA, P, true, decltype(widx)&>(gplane, splane, row_off, wsv, lut_bytes, widx,
+                                                                     a01, a2k);
         fence_accumulators(a01, a2k);
     });
     uint32_t o[P];
