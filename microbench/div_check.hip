@@ -1,4 +1,4 @@
-// Exactness check of the bilateral epilogue's division (vip_stencil.hpp div_by_sumk):
+// Exactness check of the bilateral epilogue's division (vip_exact.hpp div_by_sumk):
 //   y  = rcp(k) refined by one Newton step          -- must equal RN(1/k)
 //   q0 = RN(s * y); r = fma(-k, q0, s); q = fma(r, y, q0)  -- must equal RN(s / k)
 // (a) the reciprocal EXHAUSTIVELY for every float k in [1, 2^38) -- the sum of
@@ -25,7 +25,8 @@
 #include <cstdint>
 #include <cstdio>
 
-#include "vip_stencil.hpp"
+#include "vip_common.hpp"
+#include "vip_exact.hpp"
 
 __device__ unsigned long long g_bad[6];
 __device__ unsigned int g_exp_bad_x[16];

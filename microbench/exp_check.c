@@ -1,4 +1,4 @@
-/* CPU side of the exp check: the texture guide's table exp (vip_stencil.hpp exp_tab_f32,
+/* CPU side of the exp check: the texture guide's table exp (vip_exact.hpp exp_tab_f32,
  * restated here with the same table, constants and fma sequence -- IEEE double arithmetic,
  * so the same bits) against glibc's (float)exp((double)x), the oracle's
  * (oracle/vip_oracle.c), for EVERY float x in [0, 32). With div_check's (e) (device table

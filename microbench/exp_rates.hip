@@ -20,7 +20,7 @@
         }                                                                   \
     } while (0)
 
-#include "vip_stencil.hpp"
+#include "vip_exact.hpp"
 
 #define ITERS 512
 

@@ -94,7 +94,7 @@ def test_batch_rejects_aliasing_and_handles_empty(dev, oracle):
                                                    ("adaptive", 9, 1000, 97, 0)])
 def test_batch_last_round_pieces(dev, oracle, kind, k, w, own, inflight):
     """A multi-frame launch cuts its last round's tiles into pieces of a tile's waves, so
-    that more workgroups share that round (plan_tail, vip_stencil.hpp; the plain bilateral
+    that more workgroups share that round (plan_tail, vip_launch.hpp; the plain bilateral
     only with one frame in flight, forced here both ways). Swept over workgroup counts
     (free_cus) to get last rounds of many sizes and piece counts: every frame of a 6-frame
     launch equals its one-frame launch (which never cuts a tile), and frame 0 the oracle."""

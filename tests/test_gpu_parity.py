@@ -308,6 +308,64 @@ def test_argument_errors(dev):
     assert e.value.code == 10003
 
 
+_INVALID, _KSIZE, _ALIASING = 10001, 10002, 10003  # include/vip.h VIP_ERR_*
+# a row band of a 64 x 20 frame with one thing wrong, and what every entry point answers
+_BAD_BANDS = [
+    ("out_rows = -1", dict(out_rows=-1), _INVALID),
+    ("row_lo = -1", dict(row_lo=-1), _INVALID),
+    ("row_hi = height + 1", dict(row_hi=21), _INVALID),
+    ("row_lo == row_hi", dict(row_lo=7, row_hi=7), _INVALID),
+    ("null source", dict(src=None), _INVALID),
+    ("null destination", dict(dst=None), _INVALID),
+    ("destination == source", dict(dst="src"), _ALIASING),
+    ("destination == guide", dict(dst="guide"), _ALIASING),  # the joint filter only
+]
+
+
+@pytest.mark.parametrize("k", [5, 41])  # the templated kernels, the runtime-radius kernel
+def test_bad_row_bands_are_refused(dev, k):
+    """Every *_run_rows and *_run_rows_batch entry point, through the raw C ABI, refuses a
+    bad row band with VIP_ERR_INVALID_ARGUMENT or VIP_ERR_ALIASING before it launches
+    anything; so does a joint call on a handle whose ksize the joint filter does not run."""
+    import ctypes
+    w, h, p = 64, 20, 64 * 3
+    buf = {name: dev.empty((h, w, 3)) for name in ("src", "guide", "dst")}
+    lib = vip.lib()
+    bil, ada, big = _BilateralImpl(w, h, k), _AdaptiveImpl(w, h, k), _BilateralImpl(w, h, 49)
+    vip.launched_kernels()  # clears the list
+
+    def ptr(b, key):
+        v = b[key]
+        return None if v is None else buf[v].data_ptr()
+
+    def run(entry, b):
+        rows = (b["out_rows"], 0, b["row_lo"], b["row_hi"])
+        if entry == "joint":
+            return lib.vip_bilateral_run_rows(bil._h, ptr(b, "src"), p, ptr(b, "guide"), p, ptr(b, "dst"), p, *rows,
+                                              None)
+        if entry == "plain":
+            return lib.vip_bilateral_run_rows(bil._h, ptr(b, "src"), p, None, 0, ptr(b, "dst"), p, *rows, None)
+        if entry == "adaptive":
+            return lib.vip_adaptive_run_rows(ada._h, ptr(b, "src"), p, ptr(b, "dst"), p, *rows, None)
+        # batches of two frames, the second one carrying the fault
+        srcs = (ctypes.c_void_p * 2)(buf["src"].data_ptr(), ptr(b, "src"))
+        dsts = (ctypes.c_void_p * 2)(buf["guide"].data_ptr(), ptr(b, "dst"))
+        fn, hd = {"plain batch": (lib.vip_bilateral_run_rows_batch, bil),
+                  "adaptive batch": (lib.vip_adaptive_run_rows_batch, ada)}[entry]
+        return fn(hd._h, 2, srcs, p, dsts, p, *rows, 0, None)
+
+    for what, fault, want in _BAD_BANDS:
+        band = dict(src="src", guide="guide", dst="dst", out_rows=h, row_lo=0, row_hi=h)
+        band.update(fault)
+        for entry in ("plain", "joint", "adaptive", "plain batch", "adaptive batch"):
+            if what == "destination == guide" and entry != "joint":
+                continue  # no guide to alias
+            assert run(entry, band) == want, (what, entry)
+    good = (buf["src"].data_ptr(), p, buf["guide"].data_ptr(), p, buf["dst"].data_ptr(), p, h, 0, 0, h, None)
+    assert lib.vip_bilateral_run_rows(big._h, *good) == _KSIZE  # ksize 49 > the joint filter's 47
+    assert vip.launched_kernels() == []
+
+
 def test_full_4k_frame_rows_exact(dev, oracle):
     """C2 frame size (3840x2160, r=7): exact on rows spanning both borders and tile seams."""
     img = oracle.random_image(3840, 2160)
@@ -473,7 +531,7 @@ def test_texture_iterate_rows_band(dev, oracle):
 
 
 def test_epilogue_division_exact():
-    """The bilateral/joint epilogue divides by sumk via one reciprocal (vip_stencil.hpp
+    """The bilateral/joint epilogue divides by sumk via one reciprocal (vip_exact.hpp
     recip_exact/div_by_sumk). microbench/div_check checks RN(1/k) for EVERY float k in
     [1, 2^38) (the epilogue's sums of weights and the texture guide's 1 + exp(x) at every
     ksize) and 2^30 quotients against the IEEE divide on the GPU, the texture

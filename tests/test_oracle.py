@@ -192,7 +192,7 @@ def _fma32(a, b, c):
 
 @pytest.mark.skipif(np.finfo(np.longdouble).nmant < 63, reason="needs x87 80-bit long double")
 def test_constant_division_is_exact():
-    """The fused texture guide stage and the adaptive kernel (vip_stencil.hpp
+    """The fused texture guide stage and the adaptive kernel (vip_exact.hpp
     div_exact) divide integer box sums by ksize^2, and intensity byte sums by 3, with
     an fma-corrected reciprocal: q0 = s*rd, q = fma(fma(-q0, d, s), rd, q0). It must
     equal the correctly rounded float quotient the reference computes
@@ -249,7 +249,7 @@ def test_texture_rows_band_equals_full_frame(oracle):
 
 def test_table_exp_equals_glibc_exp(tmp_path):
     """The texture guide's alpha uses a 64-entry-table double exp on the GPU
-    (vip_stencil.hpp exp_tab_f32); microbench/exp_check restates it bit for bit (same table,
+    (vip_exact.hpp exp_tab_f32); microbench/exp_check restates it bit for bit (same table,
     constants and fma sequence) and compares it with glibc's (float)exp((double)x) -- the
     oracle's -- for EVERY float x in [0, 32), the whole range the argument can take.
     (div_check compares the device version with ocml's on the GPU.)"""

@@ -11,6 +11,7 @@
 // lanes l, l+16 of a half-wave that share a copy can meet on one bank (<= 2-way).
 // The window sums are exact integers: per-thread vertical column sums (16-bit
 // packed R|B lanes when (2R+1)^2*255 < 2^16), then a horizontal sliding window.
+#include "vip_launch.hpp"
 #include "vip_stencil.hpp"
 
 namespace vip {
@@ -319,36 +320,17 @@ static int launch_adaptive_lut(const StencilArgs& a, hipStream_t stream) {
     constexpr int LDS = lds_bytes<R, WAVES, 1, LUTW, P>() +
                         (adaptive_vbox<R, P, WAVES, LUTW>() ? 4 * TH * G::GROUPS * 4 : 0);
     static_assert(LDS <= kLdsBudget, "adaptive tile does not fit LDS");
-    auto kern = adaptive_kernel<R, WAVES, FMA, P, NE, SAT>;
-    static std::atomic<unsigned long long> attr_devs{0};
-    const bool multi = a.nframes > 1;
+    constexpr auto kern = adaptive_kernel<R, WAVES, FMA, P, NE, SAT>;
     if constexpr (R <= kBatchMaxRadius) {
-        if (multi) {
-            kern = adaptive_frames_kernel<R, WAVES, FMA, P, NE, SAT>;
-            static std::atomic<unsigned long long> attr_devs_frames{0};
-            if (const int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), LDS, attr_devs_frames, SAT))
-                return rc;
-        }
+        constexpr auto frames_kern = adaptive_frames_kernel<R, WAVES, FMA, P, NE, SAT>;
+        // the last round in pieces (C3 slab at 8 GPUs, 6 frames per launch, 8 CUs free: one
+        // stream 0.0500 -> 0.0477 ms per frame, two streams 0.0429-0.0430 both ways; at 4 GPUs
+        // on two streams 0.0960 -> 0.0939; profiles/r05_slab_batch_ab{,2}.txt)
+        return launch_persistent<kern, frames_kern, LDS, WAVES, G::TW, TH, SAT>(a, true, stream);
     } else {
-        if (multi) return VIP_ERR_INVALID_ARGUMENT;  // no multi-frame form (the batch entry point loops frames)
+        if (a.nframes > 1) return VIP_ERR_INVALID_ARGUMENT;  // no multi-frame form (the batch entry point loops frames)
+        return launch_persistent<kern, nullptr, LDS, WAVES, G::TW, TH, SAT>(a, false, stream);
     }
-    if (!multi)
-        if (const int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), LDS, attr_devs, SAT)) return rc;
-    note_launch(reinterpret_cast<const void*>(kern));
-    StencilArgs args = a;
-    args.tiles_x = (a.width + G::TW - 1) / G::TW;
-    args.tiles_frame = args.tiles_x * ((a.out_rows + TH - 1) / TH);
-    args.tiles_total = args.tiles_frame * (multi ? a.nframes : 1);
-    if (args.tiles_total == 0) return 0;
-    const int blocks = persistent_blocks(args.tiles_total, a.free_cus);
-    args.tail_full = args.tiles_total;  // no cut: every item a whole tile on the XCD map
-    args.tail_shift = 0;
-    // the last round in pieces (C3 slab at 8 GPUs, 6 frames per launch, 8 CUs free: one
-    // stream 0.0500 -> 0.0477 ms per frame, two streams 0.0429-0.0430 both ways; at 4 GPUs
-    // on two streams 0.0960 -> 0.0939; profiles/r05_slab_batch_ab{,2}.txt)
-    if (multi) plan_tail(args, blocks, WAVES);
-    launch(kern, dim3(blocks), dim3(WAVES * 64), LDS, stream, args);
-    return (int)hipGetLastError();
 }
 
 template <int R, bool FMA>

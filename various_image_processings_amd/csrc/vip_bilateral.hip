@@ -14,6 +14,7 @@
 //   from an SGPR) -> 3 x v_fma + v_add.
 // Neighbour pixels are read once per thread-row with ds_read_b128 and shared by
 // the thread's 8 horizontally adjacent outputs.
+#include "vip_launch.hpp"
 #include "vip_stencil.hpp"
 
 namespace vip {
@@ -316,38 +317,20 @@ static int launch_bilateral_w(const StencilArgs& a, hipStream_t stream) {
     constexpr int LDS = FOLD ? sat_lds_bytes<R, WAVES, PLANES, P>() : lds_bytes<R, WAVES, PLANES, NE * COPIES, P, TPR>();
     static_assert(LDS <= kLdsBudget, "tile does not fit LDS");
     constexpr bool SAT = FOLD;  // the kernel's saturating address (absolute LDS addresses)
-    auto kern = bilateral_kernel<R, WAVES, JOINT, FMA, COPIES, P, NE, FOLD, TPR, SAT>;
-    static std::atomic<unsigned long long> attr_devs{0};
-    const bool multi = !JOINT && a.nframes > 1;
+    constexpr auto kern = bilateral_kernel<R, WAVES, JOINT, FMA, COPIES, P, NE, FOLD, TPR, SAT>;
     if constexpr (!JOINT && R <= kBatchMaxRadius) {
-        if (multi) {
-            kern = bilateral_frames_kernel<R, WAVES, JOINT, FMA, COPIES, P, NE, FOLD, TPR, SAT>;
-            static std::atomic<unsigned long long> attr_devs_frames{0};
-            if (const int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), LDS, attr_devs_frames, SAT))
-                return rc;
-        }
+        constexpr auto frames_kern = bilateral_frames_kernel<R, WAVES, JOINT, FMA, COPIES, P, NE, FOLD, TPR, SAT>;
+        // the last round in pieces for one frame in flight only: with two streams the other
+        // stream's launch already fills the CUs a whole-tile last round leaves idle, and the
+        // pieces' fewer waves per CU cost more CU time (C2 slab at 8 GPUs, 6 frames per launch,
+        // 8 CUs free: one stream 0.0256-0.0258 -> 0.0250 ms per frame, two streams 0.0222-0.0225
+        // -> 0.0231-0.0233; profiles/r05_slab_batch_ab{,2}.txt)
+        return launch_persistent<kern, frames_kern, LDS, WAVES, G::TW, TH, SAT>(a, a.inflight <= 1, stream);
     } else {
-        if (multi) return VIP_ERR_INVALID_ARGUMENT;  // no multi-frame form (the batch entry point loops frames)
+        // no multi-frame form (the batch entry point loops frames); the joint filter is one frame
+        if (!JOINT && a.nframes > 1) return VIP_ERR_INVALID_ARGUMENT;
+        return launch_persistent<kern, nullptr, LDS, WAVES, G::TW, TH, SAT>(a, false, stream);
     }
-    if (!multi)
-        if (const int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), LDS, attr_devs, SAT)) return rc;
-    note_launch(reinterpret_cast<const void*>(kern));
-    StencilArgs args = a;
-    args.tiles_x = (a.width + G::TW - 1) / G::TW;
-    args.tiles_frame = args.tiles_x * ((a.out_rows + TH - 1) / TH);
-    args.tiles_total = args.tiles_frame * (multi ? a.nframes : 1);
-    if (args.tiles_total == 0) return 0;
-    const int blocks = persistent_blocks(args.tiles_total, a.free_cus);
-    args.tail_full = args.tiles_total;  // no cut: every item a whole tile on the XCD map
-    args.tail_shift = 0;
-    // the last round in pieces for one frame in flight only: with two streams the other
-    // stream's launch already fills the CUs a whole-tile last round leaves idle, and the
-    // pieces' fewer waves per CU cost more CU time (C2 slab at 8 GPUs, 6 frames per launch,
-    // 8 CUs free: one stream 0.0256-0.0258 -> 0.0250 ms per frame, two streams 0.0222-0.0225
-    // -> 0.0231-0.0233; profiles/r05_slab_batch_ab{,2}.txt)
-    if (multi && a.inflight <= 1) plan_tail(args, blocks, WAVES);
-    launch(kern, dim3(blocks), dim3(WAVES * 64), LDS, stream, args);
-    return (int)hipGetLastError();
 }
 
 template <int R, bool JOINT, bool FMA>

@@ -17,34 +17,16 @@
 #include <string>
 #include <vector>
 
-#include "vip_stencil.hpp"
+#include "vip_launch.hpp"
 
 namespace vip {
-int launch_bilateral_joint_fma(int radius, const StencilArgs& a, hipStream_t s);
-int launch_bilateral_joint_mul(int radius, const StencilArgs& a, hipStream_t s);
-int launch_bilateral_plain_fma(int radius, const StencilArgs& a, hipStream_t s);
-int launch_bilateral_plain_mul(int radius, const StencilArgs& a, hipStream_t s);
-int launch_adaptive_fma(int radius, const StencilArgs& a, hipStream_t s);
-int launch_adaptive_mul(int radius, const StencilArgs& a, hipStream_t s);
-
-static int launch_bilateral(int radius, bool joint, bool fma, const StencilArgs& a, hipStream_t s) {
-    if (joint) return fma ? launch_bilateral_joint_fma(radius, a, s) : launch_bilateral_joint_mul(radius, a, s);
+// The templated kernel of a stencil filter (VIP_FILTER_BILATERAL, _JOINT or _ADAPTIVE)
+static int launch_stencil(int filter, int radius, bool fma, const StencilArgs& a, hipStream_t s) {
+    if (filter == VIP_FILTER_JOINT)
+        return fma ? launch_bilateral_joint_fma(radius, a, s) : launch_bilateral_joint_mul(radius, a, s);
+    if (filter == VIP_FILTER_ADAPTIVE) return fma ? launch_adaptive_fma(radius, a, s) : launch_adaptive_mul(radius, a, s);
     return fma ? launch_bilateral_plain_fma(radius, a, s) : launch_bilateral_plain_mul(radius, a, s);
 }
-static int launch_adaptive(int radius, bool fma, const StencilArgs& a, hipStream_t s) {
-    return fma ? launch_adaptive_fma(radius, a, s) : launch_adaptive_mul(radius, a, s);
-}
-int launch_gradient_u8(const uint8_t* src, float* dst, int width, int height, int ch, hipStream_t stream);
-int launch_gradient_f32(const float* src, float* dst, int width, int height, int ch, bool fma, hipStream_t stream);
-int launch_blur_rtv(const uint8_t* img, const float* mag, float* blurred, float* rtv, int width, int height,
-                    int ksize, bool cpp, hipStream_t stream);
-int launch_guide(const float* blurred, const float* rtv, uint8_t* guide, int width, int height, int ksize, bool cpp,
-                 hipStream_t stream);
-int launch_texture_guide_fused(const uint8_t* img, uint8_t* guide, int width, int height, int ksize, bool cpp,
-                               hipStream_t stream);
-int launch_texture_guide_fused_rows(const uint8_t* img, uint8_t* guide, int width, int lo, int hi, int gy0, int gy1,
-                                    int ksize, bool cpp, hipStream_t stream);
-int launch_texture_iteration_fused(const StencilArgs& a, int ksize, bool cpp, hipStream_t stream);
 
 // LUT construction. CUDA profile: src/bilateral_filter_impl.cu:217-237 (float
 // coefficient, std::exp(float) == expf). CPP profile: include/cpp/bilateral_filter.hpp:13-36
@@ -137,38 +119,95 @@ static int upload_color(float** d_color, int len, float sigma_color, int numeric
     return 0;
 }
 
-static void fill_args(StencilArgs& a, int width, const uint8_t* src, size_t src_pitch, const uint8_t* guide,
-                      size_t guide_pitch, uint8_t* dst, size_t dst_pitch, int out_rows, int src_row0, int row_lo,
-                      int row_hi, const float* d_color, int lut_nonzero, const float* d_fold, const float* wsq) {
-    a.src = src;
-    a.guide = guide;
-    a.dst = dst;
-    a.src_pitch = (long long)src_pitch;
-    a.guide_pitch = (long long)guide_pitch;
-    a.dst_pitch = (long long)dst_pitch;
-    a.width = width;
-    a.out_rows = out_rows;
-    a.src_row0 = src_row0;
-    a.row_lo = row_lo;
-    a.row_hi = row_hi;
-    a.tiles_x = (width + kTW - 1) / kTW;
-    const auto al4 = [](const void* p, size_t pitch) { return ((uintptr_t)p % 4 == 0) && (pitch % 4 == 0); };
-    a.aligned = al4(src, src_pitch) && al4(guide, guide_pitch);
-    a.dst_aligned = ((uintptr_t)dst % 8 == 0) && (dst_pitch % 8 == 0);
-    a.color = d_color;
-    a.lut_nonzero = lut_nonzero;
-    a.fold = d_fold;
+// What the bilateral and adaptive handles share (vip_bilateral_s, vip_adaptive_s below)
+struct StencilHandle {
+    int width, height, ksize, radius, numerics, lut_nonzero;
+    float* d_color;
+    RtTables rt;  // runtime-radius kernel tables
+    float wsq[kWsStride * kWsStride];
+};
+
+// A band of rows as the *_run_rows entry points take it: output rows [0, out_rows) of dst are
+// source rows [src_row0, src_row0 + out_rows); every read clamps into rows [row_lo, row_hi).
+struct RowBand {
+    const uint8_t* src;
+    size_t src_pitch;
+    const uint8_t* guide;  // null: a plain filter
+    size_t guide_pitch;
+    uint8_t* dst;
+    size_t dst_pitch;
+    int out_rows, src_row0, row_lo, row_hi;
+    // the plain filters' kernels read the source as their guide: said here, nowhere else
+    const uint8_t* guide_or_src() const { return guide ? guide : src; }
+    size_t guide_or_src_pitch() const { return guide ? guide_pitch : src_pitch; }
+};
+
+// src (and guide) hold the handle's height rows: every read clamps into [row_lo, row_hi),
+// so that range must lie inside them
+static bool rows_ok(int height, int out_rows, int row_lo, int row_hi) {
+    return out_rows >= 0 && row_lo >= 0 && row_hi <= height && row_lo < row_hi;
+}
+static int check_band(int height, const RowBand& b) {
+    if (!b.src || !b.dst || !rows_ok(height, b.out_rows, b.row_lo, b.row_hi)) return VIP_ERR_INVALID_ARGUMENT;
+    if (b.dst == b.src || b.dst == b.guide_or_src()) return VIP_ERR_ALIASING;
+    return 0;
+}
+
+static bool is_aligned(const void* p, size_t pitch, size_t to) { return (uintptr_t)p % to == 0 && pitch % to == 0; }
+// Destination alignment that lets a kernel store a thread's outputs as whole words: the
+// templated kernels write 8 outputs (24 bytes) as three qwords, the runtime-radius kernel
+// 4 outputs (12 bytes) as three dwords (vip_stencil.hpp store_px_to)
+constexpr size_t kStencilDstAlign = 8, kRtDstAlign = 4;
+
+// The fields StencilArgs and RtArgs share: the band, and which accesses may be whole words
+template <class Args>
+static void band_args(Args& a, const StencilHandle& h, const RowBand& b, size_t dst_align) {
+    a.src = b.src;
+    a.guide = b.guide_or_src();
+    a.dst = b.dst;
+    a.src_pitch = (long long)b.src_pitch;
+    a.guide_pitch = (long long)b.guide_or_src_pitch();
+    a.dst_pitch = (long long)b.dst_pitch;
+    a.width = h.width;
+    a.out_rows = b.out_rows;
+    a.src_row0 = b.src_row0;
+    a.row_lo = b.row_lo;
+    a.row_hi = b.row_hi;
+    a.aligned = is_aligned(b.src, b.src_pitch, 4) && is_aligned(a.guide, b.guide_or_src_pitch(), 4);
+    a.dst_aligned = is_aligned(b.dst, b.dst_pitch, dst_align);
+    a.color = h.d_color;
+}
+
+// One frame's band for the templated kernels; `fold`: the joint kernel's folded tables or null
+static StencilArgs stencil_args(const StencilHandle& h, const RowBand& b, const float* fold = nullptr) {
+    StencilArgs a;
+    band_args(a, h, b, kStencilDstAlign);
+    a.tiles_x = (h.width + kTW - 1) / kTW;
+    a.lut_nonzero = h.lut_nonzero;
+    a.fold = fold;
     a.inflight = 1;
     a.nframes = 1;
     a.tiles_frame = 0;
     a.free_cus = 0;
-    a.tail_full = 0;  // set per launch (launch_*_ne: tiles_total, or plan_tail)
+    a.tail_full = 0;  // set per launch (launch_persistent: tiles_total, or plan_tail)
     a.tail_shift = 0;
     for (int f = 0; f < kMaxBatchFrames; ++f) {
-        a.fsrc[f] = src;
-        a.fdst[f] = dst;
+        a.fsrc[f] = b.src;
+        a.fdst[f] = b.dst;
     }
-    std::memcpy(a.ws, wsq, sizeof(a.ws));
+    std::memcpy(a.ws, h.wsq, sizeof(a.ws));
+    return a;
+}
+
+static RtArgs rt_args(const StencilHandle& h, const RowBand& b) {
+    RtArgs a{};
+    band_args(a, h, b, kRtDstAlign);
+    a.wsrow = h.rt.d;
+    a.hw = reinterpret_cast<const int*>(h.rt.d + (size_t)(2 * h.radius + 1) * h.rt.wst);
+    a.R = h.radius;
+    a.wst = h.rt.wst;
+    a.ra = h.rt.ra;
+    return a;
 }
 
 // Frames in flight on the current device, for the plain bilateral kernel's small-frame
@@ -223,20 +262,76 @@ int bilateral_forced_wide() { return g_bil_wide.load(std::memory_order_relaxed);
 
 using namespace vip;
 
-struct vip_bilateral_s {
-    int width, height, ksize, radius, numerics, lut_nonzero;
-    float* d_color;
+struct vip_bilateral_s : StencilHandle {
     float* d_fold;  // joint kernel's folded tables (small sigma_color, radius <= kSatMaxR), or null
-    RtTables rt;    // runtime-radius kernel tables
-    float wsq[kWsStride * kWsStride];
 };
 
-struct vip_adaptive_s {
-    int width, height, ksize, radius, numerics, lut_nonzero;
-    float* d_color;
-    RtTables rt;
-    float wsq[kWsStride * kWsStride];
+struct vip_adaptive_s : StencilHandle {};
+
+// Folded joint-kernel tables: table t (the t-th distinct r^2 of the disc, ascending)
+// entry d = RN(ws(r^2) * wc[d]) for d < kFoldEntries -- the product the kernel's unfolded
+// taps form (one float multiply), so results are unchanged. The kernel reads them behind
+// the saturating address (SatLut) when wc is zero from its DZ on.
+static int upload_fold(vip_bilateral_s* h, float sigma_color) {
+    const int R = h->radius;
+    float wc[768];
+    build_color(768, sigma_color, h->numerics, wc);
+    float fold[(kSatMaxR * kSatMaxR + 1) * kFoldEntries];
+    int ntab = 0;
+    for (int v = 0; v <= R * R; ++v) {
+        if (!is_disc_r2(R, v)) continue;
+        float ws = 0.f;  // the spatial weight of any tap at squared distance v
+        for (int y = 0; y <= R; ++y)
+            for (int x = 0; x <= R; ++x)
+                if (x * x + y * y == v) ws = h->wsq[y * kWsStride + x];
+        for (int d = 0; d < kFoldEntries; ++d) fold[ntab * kFoldEntries + d] = wc[d] * ws;
+        ++ntab;
+    }
+    VIP_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&h->d_fold), sizeof(float) * kFoldEntries * ntab));
+    VIP_HIP_CHECK(hipMemcpy(h->d_fold, fold, sizeof(float) * kFoldEntries * ntab, hipMemcpyHostToDevice));
+    return 0;
+}
+
+// The two create functions: the geometry, the spatial tables, the colour LUT of lut_len
+// entries, the runtime-radius tables and (bilateral) the folded tables
+struct StencilSpec {
+    int width, height, ksize;
+    float sigma_space, sigma_color;
+    int numerics;
 };
+template <class H>
+static int destroy_stencil(H* h) {
+    if (!h) return 0;
+    if constexpr (std::is_same_v<H, vip_bilateral_s>)
+        if (h->d_fold) (void)hipFree(h->d_fold);
+    if (h->rt.d) (void)hipFree(h->rt.d);
+    const int rc = h->d_color ? (int)hipFree(h->d_color) : 0;
+    delete h;
+    return rc;
+}
+template <class H>
+static int create_stencil(H** out, const StencilSpec& p, int max_ksize, int lut_len) {
+    if (!out || p.width <= 0 || p.height <= 0) return VIP_ERR_INVALID_ARGUMENT;
+    if (!valid_ksize(p.ksize, max_ksize)) return VIP_ERR_UNSUPPORTED_KSIZE;
+    H* h = new (std::nothrow) H();
+    if (!h) return (int)hipErrorOutOfMemory;
+    h->width = p.width;
+    h->height = p.height;
+    h->ksize = p.ksize;
+    h->radius = p.ksize / 2;
+    h->numerics = p.numerics == VIP_NUMERICS_CPP ? VIP_NUMERICS_CPP : VIP_NUMERICS_CUDA;
+    build_space_q(h->radius, p.sigma_space, h->numerics, h->wsq);
+    int rc = upload_color(&h->d_color, lut_len, p.sigma_color, h->numerics, &h->lut_nonzero);
+    if (!rc) rc = upload_rt_tables(h->radius, p.sigma_space, h->numerics, &h->rt);
+    if constexpr (std::is_same_v<H, vip_bilateral_s>)
+        if (!rc && h->lut_nonzero < kFoldEntries && h->radius <= kSatMaxR) rc = upload_fold(h, p.sigma_color);
+    if (rc) {
+        destroy_stencil(h);
+        return rc;
+    }
+    *out = h;
+    return 0;
+}
 
 // The handle owns three u8x3 frames: the two ping-pong frames and the guide. The
 // reference's Impl also holds f32 magnitude, blurred and rtv buffers
@@ -250,33 +345,6 @@ struct vip_texture_s {
     uint8_t* d_ping[2];
     uint8_t* d_guide;
 };
-
-static RtArgs rt_args(const RtTables& t, int radius, int width, const uint8_t* src, size_t src_pitch,
-                      const uint8_t* guide, size_t guide_pitch, uint8_t* dst, size_t dst_pitch, int out_rows,
-                      int src_row0, int row_lo, int row_hi, const float* d_color) {
-    RtArgs a{};
-    a.src = src;
-    a.guide = guide;
-    a.dst = dst;
-    a.src_pitch = (long long)src_pitch;
-    a.guide_pitch = (long long)guide_pitch;
-    a.dst_pitch = (long long)dst_pitch;
-    a.width = width;
-    a.out_rows = out_rows;
-    a.src_row0 = src_row0;
-    a.row_lo = row_lo;
-    a.row_hi = row_hi;
-    const auto al4 = [](const void* p, size_t pitch) { return ((uintptr_t)p % 4 == 0) && (pitch % 4 == 0); };
-    a.aligned = al4(src, src_pitch) && al4(guide, guide_pitch);
-    a.dst_aligned = ((uintptr_t)dst % 4 == 0) && (dst_pitch % 4 == 0);
-    a.color = d_color;
-    a.wsrow = t.d;
-    a.hw = reinterpret_cast<const int*>(t.d + (size_t)(2 * radius + 1) * t.wst);
-    a.R = radius;
-    a.wst = t.wst;
-    a.ra = t.ra;
-    return a;
-}
 
 namespace {
 thread_local const void* g_launched[16];  // distinct kernels launched since the last query
@@ -490,136 +558,98 @@ int vip_stream_wait_event(void* stream, void* event) {
 int vip_event_synchronize(void* event) { return (int)hipEventSynchronize((hipEvent_t)event); }
 
 // ---------------------------------------------------------------- bilateral
-// Folded joint-kernel tables: table t (the t-th distinct r^2 of the disc, ascending)
-// entry d = RN(ws(r^2) * wc[d]) for d < kFoldEntries -- the product the kernel's unfolded
-// taps form (one float multiply), so results are unchanged. The kernel reads them behind
-// the saturating address (SatLut) when wc is zero from its DZ on.
-static int upload_fold(vip_bilateral_s* h, float sigma_color) {
-    const int R = h->radius;
-    float wc[768];
-    build_color(768, sigma_color, h->numerics, wc);
-    float fold[(kSatMaxR * kSatMaxR + 1) * kFoldEntries];
-    int ntab = 0;
-    for (int v = 0; v <= R * R; ++v) {
-        if (!is_disc_r2(R, v)) continue;
-        float ws = 0.f;  // the spatial weight of any tap at squared distance v
-        for (int y = 0; y <= R; ++y)
-            for (int x = 0; x <= R; ++x)
-                if (x * x + y * y == v) ws = h->wsq[y * kWsStride + x];
-        for (int d = 0; d < kFoldEntries; ++d) fold[ntab * kFoldEntries + d] = wc[d] * ws;
-        ++ntab;
-    }
-    VIP_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&h->d_fold), sizeof(float) * kFoldEntries * ntab));
-    VIP_HIP_CHECK(hipMemcpy(h->d_fold, fold, sizeof(float) * kFoldEntries * ntab, hipMemcpyHostToDevice));
-    return 0;
-}
-
 int vip_bilateral_create(vip_bilateral_t* out, int width, int height, int ksize, float sigma_space, float sigma_color,
                          int numerics) {
-    if (!out || width <= 0 || height <= 0) return VIP_ERR_INVALID_ARGUMENT;
-    if (!valid_ksize(ksize, kMaxKsizeBilateral)) return VIP_ERR_UNSUPPORTED_KSIZE;
-    auto* h = new (std::nothrow) vip_bilateral_s();
-    if (!h) return (int)hipErrorOutOfMemory;
-    h->width = width;
-    h->height = height;
-    h->ksize = ksize;
-    h->radius = ksize / 2;
-    h->numerics = numerics == VIP_NUMERICS_CPP ? VIP_NUMERICS_CPP : VIP_NUMERICS_CUDA;
-    build_space_q(h->radius, sigma_space, h->numerics, h->wsq);
-    int rc = upload_color(&h->d_color, 768, sigma_color, h->numerics, &h->lut_nonzero);
-    if (!rc) rc = upload_rt_tables(h->radius, sigma_space, h->numerics, &h->rt);
-    if (!rc && h->lut_nonzero < kFoldEntries && h->radius <= kSatMaxR) rc = upload_fold(h, sigma_color);
-    if (rc) {
-        vip_bilateral_destroy(h);
-        return rc;
-    }
-    *out = h;
-    return 0;
+    return create_stencil(out, {width, height, ksize, sigma_space, sigma_color, numerics}, kMaxKsizeBilateral, 768);
 }
 
-int vip_bilateral_destroy(vip_bilateral_t h) {
-    if (!h) return 0;
-    if (h->d_fold) (void)hipFree(h->d_fold);
-    if (h->rt.d) (void)hipFree(h->rt.d);
-    const int rc = h->d_color ? (int)hipFree(h->d_color) : 0;
-    delete h;
-    return rc;
+int vip_bilateral_destroy(vip_bilateral_t h) { return destroy_stencil(h); }
+
+// One band through a stencil filter of handle h: the runtime-radius kernel or the
+// templated one. `fold`: the joint filter's folded tables, or null.
+static int run_band(const StencilHandle& h, int filter, const RowBand& b, const float* fold, hipStream_t s) {
+    const bool fma = h.numerics == VIP_NUMERICS_CUDA;
+    if (use_runtime_kernel(h.radius))
+        return launch_stencil_rt(rt_args(h, b), filter == VIP_FILTER_JOINT, filter == VIP_FILTER_ADAPTIVE, fma, s);
+    StencilArgs a = stencil_args(h, b, fold);
+    if (filter == VIP_FILTER_BILATERAL) a.inflight = frames_in_flight(s);
+    return launch_stencil(filter, h.radius, fma, a, s);
 }
 
 int vip_bilateral_run_rows(vip_bilateral_t h, const uint8_t* d_src, size_t src_pitch, const uint8_t* d_guide,
                            size_t guide_pitch, uint8_t* d_dst, size_t dst_pitch, int out_rows, int src_row0,
                            int row_lo, int row_hi, void* stream) {
-    // d_src (and d_guide) hold the handle's height rows: every read clamps into
-    // [row_lo, row_hi), so that range must lie inside them
-    if (!h || !d_src || !d_dst || out_rows < 0 || row_lo < 0 || row_hi > h->height || row_lo >= row_hi)
-        return VIP_ERR_INVALID_ARGUMENT;
-    if (d_dst == d_src || (d_guide && d_dst == d_guide)) return VIP_ERR_ALIASING;
+    if (!h) return VIP_ERR_INVALID_ARGUMENT;
+    const RowBand b{d_src, src_pitch, d_guide, guide_pitch, d_dst, dst_pitch, out_rows, src_row0, row_lo, row_hi};
+    if (const int rc = check_band(h->height, b)) return rc;
     const bool joint = d_guide != nullptr;
     if (joint && h->ksize > kMaxKsizeJoint) return VIP_ERR_UNSUPPORTED_KSIZE;
-    if (use_runtime_kernel(h->radius)) {
-        const RtArgs r = rt_args(h->rt, h->radius, h->width, d_src, src_pitch, joint ? d_guide : d_src,
-                                 joint ? guide_pitch : src_pitch, d_dst, dst_pitch, out_rows, src_row0, row_lo,
-                                 row_hi, h->d_color);
-        return launch_stencil_rt(r, joint, false, h->numerics == VIP_NUMERICS_CUDA, (hipStream_t)stream);
-    }
-    StencilArgs a;
-    fill_args(a, h->width, d_src, src_pitch, joint ? d_guide : d_src, joint ? guide_pitch : src_pitch, d_dst,
-              dst_pitch, out_rows, src_row0, row_lo, row_hi, h->d_color, h->lut_nonzero, joint ? h->d_fold : nullptr,
-              h->wsq);
-    if (!joint) a.inflight = frames_in_flight((hipStream_t)stream);
-    return launch_bilateral(h->radius, joint, h->numerics == VIP_NUMERICS_CUDA, a, (hipStream_t)stream);
+    return run_band(*h, joint ? VIP_FILTER_JOINT : VIP_FILTER_BILATERAL, b, joint ? h->d_fold : nullptr,
+                    (hipStream_t)stream);
 }
 
-// Frames [f0, f0 + m) of a batch in one StencilArgs (m <= kMaxBatchFrames): frame 0's
-// pointers in src/dst, every frame's in fsrc/fdst; dword tile loads / qword stores only
-// when every frame allows them.
-static void fill_batch(StencilArgs& a, int m, const uint8_t* const* srcs, size_t src_pitch, uint8_t* const* dsts,
-                       size_t dst_pitch) {
-    a.nframes = m;
+// The frames of a *_run_rows_batch call, or a run of them
+struct Batch {
+    int n;
+    const uint8_t* const* srcs;
+    uint8_t* const* dsts;
+};
+
+// Frames t (t.n <= kMaxBatchFrames) in one StencilArgs built for frame 0: every frame's
+// pointers in fsrc/fdst; dword tile loads / qword stores only when every frame allows them.
+static void fill_batch(StencilArgs& a, const Batch& t, const RowBand& b) {
+    a.nframes = t.n;
     for (int f = 0; f < kMaxBatchFrames; ++f) {
-        a.fsrc[f] = srcs[f < m ? f : 0];
-        a.fdst[f] = dsts[f < m ? f : 0];
-        a.aligned = a.aligned && (uintptr_t)a.fsrc[f] % 4 == 0 && src_pitch % 4 == 0;
-        a.dst_aligned = a.dst_aligned && (uintptr_t)a.fdst[f] % 8 == 0 && dst_pitch % 8 == 0;
+        a.fsrc[f] = t.srcs[f < t.n ? f : 0];
+        a.fdst[f] = t.dsts[f < t.n ? f : 0];
+        a.aligned = a.aligned && is_aligned(a.fsrc[f], b.src_pitch, 4);
+        a.dst_aligned = a.dst_aligned && is_aligned(a.fdst[f], b.dst_pitch, kStencilDstAlign);
     }
 }
 
 // Batch arguments: every pointer set, no output that is also an input of the batch.
-static int check_batch(int n, const uint8_t* const* srcs, uint8_t* const* dsts) {
-    if (n < 0 || (n > 0 && (!srcs || !dsts))) return VIP_ERR_INVALID_ARGUMENT;
-    for (int f = 0; f < n; ++f)
-        if (!srcs[f] || !dsts[f]) return VIP_ERR_INVALID_ARGUMENT;
-    for (int f = 0; f < n; ++f)
-        for (int g = 0; g < n; ++g)
-            if (dsts[f] == srcs[g]) return VIP_ERR_ALIASING;
+static int check_batch(const Batch& t) {
+    if (t.n < 0 || (t.n > 0 && (!t.srcs || !t.dsts))) return VIP_ERR_INVALID_ARGUMENT;
+    for (int f = 0; f < t.n; ++f)
+        if (!t.srcs[f] || !t.dsts[f]) return VIP_ERR_INVALID_ARGUMENT;
+    for (int f = 0; f < t.n; ++f)
+        for (int g = 0; g < t.n; ++g)
+            if (t.dsts[f] == t.srcs[g]) return VIP_ERR_ALIASING;
+    return 0;
+}
+
+// The two *_run_rows_batch entry points (filter: VIP_FILTER_BILATERAL or _ADAPTIVE; only the
+// plain bilateral tiling looks at the frames in flight). `b`: the common band, pointers unset.
+static int run_batch(const StencilHandle& h, int filter, const Batch& t, RowBand b, int free_cus, hipStream_t s) {
+    if (!rows_ok(h.height, b.out_rows, b.row_lo, b.row_hi) || free_cus < 0) return VIP_ERR_INVALID_ARGUMENT;
+    if (const int rc = check_batch(t)) return rc;
+    if (use_runtime_kernel(h.radius) || h.radius > kBatchMaxRadius) {  // no multi-frame form: frame by frame
+        for (int f = 0; f < t.n; ++f) {
+            b.src = t.srcs[f];
+            b.dst = t.dsts[f];
+            if (const int rc = run_band(h, filter, b, nullptr, s)) return rc;
+        }
+        return 0;
+    }
+    for (int f0 = 0; f0 < t.n; f0 += kMaxBatchFrames) {
+        const Batch run{t.n - f0 < kMaxBatchFrames ? t.n - f0 : kMaxBatchFrames, t.srcs + f0, t.dsts + f0};
+        b.src = run.srcs[0];
+        b.dst = run.dsts[0];
+        StencilArgs a = stencil_args(h, b);
+        fill_batch(a, run, b);
+        if (filter == VIP_FILTER_BILATERAL) a.inflight = frames_in_flight(s);
+        a.free_cus = free_cus;
+        if (const int rc = launch_stencil(filter, h.radius, h.numerics == VIP_NUMERICS_CUDA, a, s)) return rc;
+    }
     return 0;
 }
 
 int vip_bilateral_run_rows_batch(vip_bilateral_t h, int n, const uint8_t* const* d_srcs, size_t src_pitch,
                                  uint8_t* const* d_dsts, size_t dst_pitch, int out_rows, int src_row0, int row_lo,
                                  int row_hi, int free_cus, void* stream) {
-    if (!h || out_rows < 0 || row_lo < 0 || row_hi > h->height || row_lo >= row_hi || free_cus < 0)
-        return VIP_ERR_INVALID_ARGUMENT;
-    if (const int rc = check_batch(n, d_srcs, d_dsts)) return rc;
-    const hipStream_t s = (hipStream_t)stream;
-    if (use_runtime_kernel(h->radius) || h->radius > kBatchMaxRadius) {  // no multi-frame form: frame by frame
-        for (int f = 0; f < n; ++f)
-            if (const int rc = vip_bilateral_run_rows(h, d_srcs[f], src_pitch, nullptr, 0, d_dsts[f], dst_pitch,
-                                                      out_rows, src_row0, row_lo, row_hi, stream))
-                return rc;
-        return 0;
-    }
-    for (int f0 = 0; f0 < n; f0 += kMaxBatchFrames) {
-        const int m = n - f0 < kMaxBatchFrames ? n - f0 : kMaxBatchFrames;
-        StencilArgs a;
-        fill_args(a, h->width, d_srcs[f0], src_pitch, d_srcs[f0], src_pitch, d_dsts[f0], dst_pitch, out_rows,
-                  src_row0, row_lo, row_hi, h->d_color, h->lut_nonzero, nullptr, h->wsq);
-        fill_batch(a, m, d_srcs + f0, src_pitch, d_dsts + f0, dst_pitch);
-        a.inflight = frames_in_flight(s);
-        a.free_cus = free_cus;
-        if (const int rc = launch_bilateral(h->radius, false, h->numerics == VIP_NUMERICS_CUDA, a, s)) return rc;
-    }
-    return 0;
+    if (!h) return VIP_ERR_INVALID_ARGUMENT;
+    const RowBand b{nullptr, src_pitch, nullptr, 0, nullptr, dst_pitch, out_rows, src_row0, row_lo, row_hi};
+    return run_batch(*h, VIP_FILTER_BILATERAL, {n, d_srcs, d_dsts}, b, free_cus, (hipStream_t)stream);
 }
 
 int vip_bilateral_run(vip_bilateral_t h, const uint8_t* d_src, size_t src_pitch, uint8_t* d_dst, size_t dst_pitch,
@@ -639,75 +669,26 @@ int vip_joint_bilateral_run(vip_bilateral_t h, const uint8_t* d_src, size_t src_
 // ---------------------------------------------------------------- adaptive
 int vip_adaptive_create(vip_adaptive_t* out, int width, int height, int ksize, float sigma_space, float sigma_color,
                         int numerics) {
-    if (!out || width <= 0 || height <= 0) return VIP_ERR_INVALID_ARGUMENT;
-    if (!valid_ksize(ksize, kMaxKsizeAdaptive)) return VIP_ERR_UNSUPPORTED_KSIZE;
-    auto* h = new (std::nothrow) vip_adaptive_s();
-    if (!h) return (int)hipErrorOutOfMemory;
-    h->width = width;
-    h->height = height;
-    h->ksize = ksize;
-    h->radius = ksize / 2;
-    h->numerics = numerics == VIP_NUMERICS_CPP ? VIP_NUMERICS_CPP : VIP_NUMERICS_CUDA;
-    build_space_q(h->radius, sigma_space, h->numerics, h->wsq);
     // the reference's table is 512*3 long (src/adaptive_bilateral_filter_impl.cu:5)
-    int rc = upload_color(&h->d_color, 1536, sigma_color, h->numerics, &h->lut_nonzero);
-    if (!rc) rc = upload_rt_tables(h->radius, sigma_space, h->numerics, &h->rt);
-    if (rc) {
-        vip_adaptive_destroy(h);
-        return rc;
-    }
-    *out = h;
-    return 0;
+    return create_stencil(out, {width, height, ksize, sigma_space, sigma_color, numerics}, kMaxKsizeAdaptive, 1536);
 }
 
-int vip_adaptive_destroy(vip_adaptive_t h) {
-    if (!h) return 0;
-    if (h->rt.d) (void)hipFree(h->rt.d);
-    const int rc = h->d_color ? (int)hipFree(h->d_color) : 0;
-    delete h;
-    return rc;
-}
+int vip_adaptive_destroy(vip_adaptive_t h) { return destroy_stencil(h); }
 
 int vip_adaptive_run_rows(vip_adaptive_t h, const uint8_t* d_src, size_t src_pitch, uint8_t* d_dst, size_t dst_pitch,
                           int out_rows, int src_row0, int row_lo, int row_hi, void* stream) {
-    if (!h || !d_src || !d_dst || out_rows < 0 || row_lo < 0 || row_hi > h->height || row_lo >= row_hi)
-        return VIP_ERR_INVALID_ARGUMENT;
-    if (d_dst == d_src) return VIP_ERR_ALIASING;
-    if (use_runtime_kernel(h->radius)) {
-        const RtArgs r = rt_args(h->rt, h->radius, h->width, d_src, src_pitch, d_src, src_pitch, d_dst, dst_pitch,
-                                 out_rows, src_row0, row_lo, row_hi, h->d_color);
-        return launch_stencil_rt(r, false, true, h->numerics == VIP_NUMERICS_CUDA, (hipStream_t)stream);
-    }
-    StencilArgs a;
-    fill_args(a, h->width, d_src, src_pitch, d_src, src_pitch, d_dst, dst_pitch, out_rows, src_row0, row_lo, row_hi,
-              h->d_color, h->lut_nonzero, nullptr, h->wsq);
-    return launch_adaptive(h->radius, h->numerics == VIP_NUMERICS_CUDA, a, (hipStream_t)stream);
+    if (!h) return VIP_ERR_INVALID_ARGUMENT;
+    const RowBand b{d_src, src_pitch, nullptr, 0, d_dst, dst_pitch, out_rows, src_row0, row_lo, row_hi};
+    if (const int rc = check_band(h->height, b)) return rc;
+    return run_band(*h, VIP_FILTER_ADAPTIVE, b, nullptr, (hipStream_t)stream);
 }
 
 int vip_adaptive_run_rows_batch(vip_adaptive_t h, int n, const uint8_t* const* d_srcs, size_t src_pitch,
                                 uint8_t* const* d_dsts, size_t dst_pitch, int out_rows, int src_row0, int row_lo,
                                 int row_hi, int free_cus, void* stream) {
-    if (!h || out_rows < 0 || row_lo < 0 || row_hi > h->height || row_lo >= row_hi || free_cus < 0)
-        return VIP_ERR_INVALID_ARGUMENT;
-    if (const int rc = check_batch(n, d_srcs, d_dsts)) return rc;
-    const hipStream_t s = (hipStream_t)stream;
-    if (use_runtime_kernel(h->radius) || h->radius > kBatchMaxRadius) {  // no multi-frame form: frame by frame
-        for (int f = 0; f < n; ++f)
-            if (const int rc = vip_adaptive_run_rows(h, d_srcs[f], src_pitch, d_dsts[f], dst_pitch, out_rows, src_row0,
-                                                     row_lo, row_hi, stream))
-                return rc;
-        return 0;
-    }
-    for (int f0 = 0; f0 < n; f0 += kMaxBatchFrames) {
-        const int m = n - f0 < kMaxBatchFrames ? n - f0 : kMaxBatchFrames;
-        StencilArgs a;
-        fill_args(a, h->width, d_srcs[f0], src_pitch, d_srcs[f0], src_pitch, d_dsts[f0], dst_pitch, out_rows,
-                  src_row0, row_lo, row_hi, h->d_color, h->lut_nonzero, nullptr, h->wsq);
-        fill_batch(a, m, d_srcs + f0, src_pitch, d_dsts + f0, dst_pitch);
-        a.free_cus = free_cus;
-        if (const int rc = launch_adaptive(h->radius, h->numerics == VIP_NUMERICS_CUDA, a, s)) return rc;
-    }
-    return 0;
+    if (!h) return VIP_ERR_INVALID_ARGUMENT;
+    const RowBand b{nullptr, src_pitch, nullptr, 0, nullptr, dst_pitch, out_rows, src_row0, row_lo, row_hi};
+    return run_batch(*h, VIP_FILTER_ADAPTIVE, {n, d_srcs, d_dsts}, b, free_cus, (hipStream_t)stream);
 }
 
 int vip_adaptive_run(vip_adaptive_t h, const uint8_t* d_src, size_t src_pitch, uint8_t* d_dst, size_t dst_pitch,
@@ -814,11 +795,9 @@ static int texture_run(vip_texture_t h, const uint8_t* d_src, uint8_t* d_dst, vo
         if (events) VIP_HIP_CHECK(hipEventRecord((hipEvent_t)events[2 * it], s));
         int rc;
         if (h->mode == VIP_TEXTURE_FUSED) {  // guide + JBF in one launch, the guide stays in LDS
-            const vip_bilateral_s* j = h->jbf;
-            StencilArgs a;
-            fill_args(a, h->width, cur, pitch, cur, pitch, next, pitch, h->height, 0, 0, h->height, j->d_color,
-                      j->lut_nonzero, nullptr, j->wsq);
-            rc = launch_texture_iteration_fused(a, h->ksize, h->numerics == VIP_NUMERICS_CPP, s);
+            const RowBand b{cur, pitch, nullptr, 0, next, pitch, h->height, 0, 0, h->height};
+            rc = launch_texture_iteration_fused(stencil_args(*h->jbf, b), h->ksize, h->numerics == VIP_NUMERICS_CPP,
+                                                s);
             if (!rc && events) rc = (int)hipEventRecord((hipEvent_t)events[2 * it + 1], s);
         } else {
             rc = launch_texture_guide_fused(cur, h->d_guide, h->width, h->height, h->ksize,
@@ -860,8 +839,8 @@ int vip_texture_halo_rows(int ksize) {
 // vip_texture_halo_rows(k) valid rows around the output rows.
 int vip_texture_iterate_rows(vip_texture_t h, const uint8_t* d_src, uint8_t* d_dst, size_t dst_pitch, int out_row0,
                              int out_rows, int row_lo, int row_hi, void* stream) {
-    if (!h || !d_src || !d_dst || out_rows < 0 || row_lo < 0 || row_hi > h->height || row_lo >= row_hi ||
-        out_row0 < row_lo || out_row0 + out_rows > row_hi)
+    if (!h || !d_src || !d_dst || !rows_ok(h->height, out_rows, row_lo, row_hi) || out_row0 < row_lo ||
+        out_row0 + out_rows > row_hi)
         return VIP_ERR_INVALID_ARGUMENT;
     if (out_rows == 0) return 0;
     const size_t pitch = (size_t)h->width * 3;

@@ -32,10 +32,10 @@ int comm_fail(ncclResult_t r, const char* what) {
     return VIP_ERR_COMM;
 }
 
-#define VIP_HIP_TRY(expr)                                 \
-    do {                                                  \
-        const hipError_t e_ = (expr);                     \
-        if (e_ != hipSuccess) return (int)e_;             \
+#define VIP_TRY(expr)                   \
+    do {                                \
+        const int e_ = (int)(expr);     \
+        if (e_) return e_;              \
     } while (0)
 
 // Polls a non-blocking communicator until its pending operation (initialisation or
@@ -148,7 +148,7 @@ struct FilterSpec {
 
 // Filter handle, stream and events of a shard on the current device (geometry set).
 int init_shard(vip_shard_s* h, const FilterSpec& f) {
-    VIP_HIP_TRY(hipGetDevice(&h->device));
+    VIP_TRY(hipGetDevice(&h->device));
     int rc = 0;
     if (h->kind == VIP_FILTER_TEXTURE) {
         rc = vip_texture_create(&h->tex, h->width, h->slab_rows(), h->ksize, h->nitr, h->numerics);
@@ -162,9 +162,9 @@ int init_shard(vip_shard_s* h, const FilterSpec& f) {
                                   h->numerics);
     }
     if (rc) return rc;
-    VIP_HIP_TRY(hipStreamCreateWithFlags(&h->comm, hipStreamNonBlocking));
-    VIP_HIP_TRY(hipEventCreateWithFlags(&h->ev_in, hipEventDisableTiming));
-    VIP_HIP_TRY(hipEventCreateWithFlags(&h->ev_x, hipEventDisableTiming));
+    VIP_TRY(hipStreamCreateWithFlags(&h->comm, hipStreamNonBlocking));
+    VIP_TRY(hipEventCreateWithFlags(&h->ev_in, hipEventDisableTiming));
+    VIP_TRY(hipEventCreateWithFlags(&h->ev_x, hipEventDisableTiming));
     return 0;
 }
 
@@ -254,23 +254,30 @@ int filter_rows(const vip_shard_s* h, uint8_t* slab, uint8_t* out, size_t out_pi
     return vip_bilateral_run_rows(h->bil, slab, h->pitch(), nullptr, 0, o, out_pitch, n, h->r + row0, lo, hi, s);
 }
 
+// The frames of one run call on one shard: slab f is filtered into out f
+struct Frames {
+    int n;
+    uint8_t* const* slabs;
+    uint8_t* const* outs;
+    size_t out_pitch;
+};
+
 // Every own row of n frames: one launch per frame, or (vip_shard_set_frames_launch, plain
 // and adaptive filters) one launch per 6 frames (vip_*_run_rows_batch: the launch prologue
 // and tail once per launch).
-int filter_frames(const vip_shard_s* h, int n, uint8_t* const* slabs, uint8_t* const* outs, size_t out_pitch,
-                  hipStream_t s) {
-    if (h->kind == VIP_FILTER_TEXTURE || n == 1 || !h->frames_launch) {
-        for (int f = 0; f < n; ++f)
-            if (const int rc = filter_rows(h, slabs[f], outs[f], out_pitch, 0, h->own, s)) return rc;
+int filter_frames(const vip_shard_s* h, const Frames& fr, hipStream_t s) {
+    if (h->kind == VIP_FILTER_TEXTURE || fr.n == 1 || !h->frames_launch) {
+        for (int f = 0; f < fr.n; ++f)
+            if (const int rc = filter_rows(h, fr.slabs[f], fr.outs[f], fr.out_pitch, 0, h->own, s)) return rc;
         return 0;
     }
     int lo, hi;
     clamp_range(h, &lo, &hi);
-    const uint8_t* const* srcs = const_cast<const uint8_t* const*>(slabs);
+    const uint8_t* const* srcs = const_cast<const uint8_t* const*>(fr.slabs);
     if (h->kind == VIP_FILTER_ADAPTIVE)
-        return vip_adaptive_run_rows_batch(h->ada, n, srcs, h->pitch(), outs, out_pitch, h->own, h->r, lo, hi,
-                                           h->free_cus, s);
-    return vip_bilateral_run_rows_batch(h->bil, n, srcs, h->pitch(), outs, out_pitch, h->own, h->r, lo, hi,
+        return vip_adaptive_run_rows_batch(h->ada, fr.n, srcs, h->pitch(), fr.outs, fr.out_pitch, h->own, h->r, lo,
+                                           hi, h->free_cus, s);
+    return vip_bilateral_run_rows_batch(h->bil, fr.n, srcs, h->pitch(), fr.outs, fr.out_pitch, h->own, h->r, lo, hi,
                                         h->free_cus, s);
 }
 
@@ -317,6 +324,23 @@ int group_end(vip_shard_s* const* hs, int n) {
 // Record `ev` on `s` when the caller asked for timing events.
 int mark(void* const* events, int k, hipStream_t s) {
     return events ? (int)hipEventRecord((hipEvent_t)events[k], s) : 0;
+}
+
+// The launches of a shard whose halos are in once `halos` fires: one launch over the own rows
+// after it, or (split) the interiors under the exchange, then every frame's edge bands.
+// events[2]: halos in on the filter stream (split: the interiors enqueued), events[3]: the end.
+int after_halos(const vip_shard_s* h, const Frames& fr, hipStream_t s, hipEvent_t halos, void* const* events) {
+    if (!h->split) {
+        VIP_TRY(hipStreamWaitEvent(s, halos, 0));
+        VIP_TRY(mark(events, 2, s));
+        VIP_TRY(filter_frames(h, fr, s));
+        return mark(events, 3, s);
+    }
+    for (int f = 0; f < fr.n; ++f) VIP_TRY(interior(h, fr.slabs[f], fr.outs[f], fr.out_pitch, s));
+    VIP_TRY(mark(events, 2, s));
+    VIP_TRY(hipStreamWaitEvent(s, halos, 0));
+    for (int f = 0; f < fr.n; ++f) VIP_TRY(edges(h, fr.slabs[f], fr.outs[f], fr.out_pitch, s));
+    return mark(events, 3, s);
 }
 
 struct DeviceGuard {  // restores the caller's current device
@@ -609,43 +633,38 @@ static int check_run(vip_shard_t h, uint8_t* slab, uint8_t* out, size_t out_pitc
     return 0;
 }
 
-// One frame's work enqueued on `s` (and the communication stream), device already set.
+// The frames' work enqueued on `s` (and the communication stream), device already set: own
+// rows written (ev_in) -> the communication stream waits for them -> one RCCL group with every
+// frame's sends and receives -> halos in (ev_x) -> the launches (after_halos). The exchange
+// goes first, so its kernel is dispatched ahead of the interior launch. `events`:
+// vip_shard_run_timed's four, or null. *exchanged is set once the group is enqueued (RCCL has
+// then connected the peers: vip_shard_s::warm).
+static int enqueue_frames(vip_shard_t h, const Frames& fr, hipStream_t s, void* const* events,
+                          bool* exchanged = nullptr) {
+    VIP_TRY(mark(events, 0, s));
+    if (!h->above() && !h->below()) {  // no neighbours: the launches only
+        VIP_TRY(mark(events, 1, s));
+        VIP_TRY(filter_frames(h, fr, s));
+        VIP_TRY(mark(events, 2, s));
+        return mark(events, 3, s);
+    }
+    VIP_TRY(hipEventRecord(h->ev_in, s));
+    VIP_TRY(hipStreamWaitEvent(h->comm, h->ev_in, 0));
+    if (const ncclResult_t e = ncclGroupStart()) return comm_fail(e, "ncclGroupStart");
+    int rc = 0;
+    for (int f = 0; f < fr.n && !rc; ++f) rc = enqueue_p2p(h, fr.slabs[f]);
+    const int rc2 = group_end(&h, 1);
+    if (rc || rc2) return rc ? rc : rc2;
+    if (exchanged) *exchanged = true;
+    VIP_TRY(mark(events, 1, h->comm));
+    VIP_TRY(hipEventRecord(h->ev_x, h->comm));
+    return after_halos(h, fr, s, h->ev_x, events);
+}
+
+// One frame: vip_shard_run, vip_shard_run_timed and the sequence graph mode captures
 static int enqueue_run(vip_shard_t h, uint8_t* slab, uint8_t* out, size_t out_pitch, hipStream_t s,
                        void* const* events) {
-    int rc = mark(events, 0, s);
-    if (!rc && !h->above() && !h->below()) {  // no neighbours: one launch over the own rows
-        rc = mark(events, 1, s);
-        if (!rc) rc = filter_rows(h, slab, out, out_pitch, 0, h->own, s);
-        if (!rc) rc = mark(events, 2, s);
-        if (!rc) rc = mark(events, 3, s);
-        return rc;
-    }
-    // exchange first on the communication stream (its kernel is dispatched ahead of the
-    // interior launch), then the interior on the caller's stream, then the edges after
-    // the halos
-    if (!rc) rc = (int)hipEventRecord(h->ev_in, s);
-    if (!rc) rc = (int)hipStreamWaitEvent(h->comm, h->ev_in, 0);
-    if (!rc) {
-        if (const ncclResult_t e = ncclGroupStart()) rc = comm_fail(e, "ncclGroupStart");
-        if (!rc) rc = enqueue_p2p(h, slab);
-        const int rc2 = group_end(&h, 1);
-        if (!rc) rc = rc2;
-    }
-    if (!rc) rc = mark(events, 1, h->comm);
-    if (!rc) rc = (int)hipEventRecord(h->ev_x, h->comm);
-    if (!h->split) {  // one launch over the own rows once the halos are in
-        if (!rc) rc = (int)hipStreamWaitEvent(s, h->ev_x, 0);
-        if (!rc) rc = mark(events, 2, s);  // halos in, on the filter stream
-        if (!rc) rc = filter_rows(h, slab, out, out_pitch, 0, h->own, s);
-        if (!rc) rc = mark(events, 3, s);
-        return rc;
-    }
-    if (!rc) rc = interior(h, slab, out, out_pitch, s);
-    if (!rc) rc = mark(events, 2, s);
-    if (!rc) rc = (int)hipStreamWaitEvent(s, h->ev_x, 0);
-    if (!rc) rc = edges(h, slab, out, out_pitch, s);
-    if (!rc) rc = mark(events, 3, s);
-    return rc;
+    return enqueue_frames(h, Frames{1, &slab, &out, out_pitch}, s, events);
 }
 
 int vip_shard_run_batch(vip_shard_t h, int n, uint8_t* const* d_slabs, uint8_t* const* d_outs, size_t out_pitch,
@@ -655,30 +674,11 @@ int vip_shard_run_batch(vip_shard_t h, int n, uint8_t* const* d_slabs, uint8_t* 
     for (int f = 0; f < n; ++f)
         if (!d_slabs[f] || !d_outs[f]) return VIP_ERR_INVALID_ARGUMENT;
     DeviceGuard guard;
-    const hipStream_t s = (hipStream_t)stream;
-    VIP_HIP_TRY(hipSetDevice(h->device));
-    if (!h->above() && !h->below())  // no neighbours: the launches only
-        return filter_frames(h, n, d_slabs, d_outs, out_pitch, s);
-    // every frame's own rows written -> one group with all the halos on the communication stream
-    VIP_HIP_TRY(hipEventRecord(h->ev_in, s));
-    VIP_HIP_TRY(hipStreamWaitEvent(h->comm, h->ev_in, 0));
-    int rc = 0;
-    if (const ncclResult_t e = ncclGroupStart()) return comm_fail(e, "ncclGroupStart");
-    for (int f = 0; f < n && !rc; ++f) rc = enqueue_p2p(h, d_slabs[f]);
-    const int rc2 = group_end(&h, 1);
-    if (rc || rc2) return rc ? rc : rc2;
-    h->warm = true;
-    VIP_HIP_TRY(hipEventRecord(h->ev_x, h->comm));
-    if (!h->split) {
-        VIP_HIP_TRY(hipStreamWaitEvent(s, h->ev_x, 0));
-        return filter_frames(h, n, d_slabs, d_outs, out_pitch, s);
-    }
-    for (int f = 0; f < n; ++f)  // interiors under the exchange, then every frame's edge bands
-        if ((rc = interior(h, d_slabs[f], d_outs[f], out_pitch, s))) return rc;
-    VIP_HIP_TRY(hipStreamWaitEvent(s, h->ev_x, 0));
-    for (int f = 0; f < n; ++f)
-        if ((rc = edges(h, d_slabs[f], d_outs[f], out_pitch, s))) return rc;
-    return 0;
+    VIP_TRY(hipSetDevice(h->device));
+    bool exchanged = false;
+    const int rc = enqueue_frames(h, Frames{n, d_slabs, d_outs, out_pitch}, (hipStream_t)stream, nullptr, &exchanged);
+    if (exchanged) h->warm = true;
+    return rc;
 }
 
 // Graph mode: the frame's whole sequence (own rows written -> exchange on the
@@ -690,7 +690,7 @@ int vip_shard_run_batch(vip_shard_t h, int n, uint8_t* const* d_slabs, uint8_t* 
 static int run_graph(vip_shard_t h, uint8_t* slab, uint8_t* out, size_t out_pitch, hipStream_t s) {
     for (const auto& g : h->graphs)
         if (g.slab == slab && g.out == out && g.pitch == out_pitch && g.stream == s) {
-            VIP_HIP_TRY(hipGraphLaunch(g.exec, s));
+            VIP_TRY(hipGraphLaunch(g.exec, s));
             return (int)hipEventRecord(g.done, s);
         }
     if (h->graphs.size() >= kMaxGraphs) {  // the oldest graph may still be in flight: free_graph waits
@@ -731,31 +731,31 @@ static int run_graph(vip_shard_t h, uint8_t* slab, uint8_t* out, size_t out_pitc
         return enqueue_run(h, slab, out, out_pitch, s, nullptr);
     }
     h->graphs.push_back({slab, out, out_pitch, s, exec, done});
-    VIP_HIP_TRY(hipGraphLaunch(exec, s));
+    VIP_TRY(hipGraphLaunch(exec, s));
     return (int)hipEventRecord(done, s);
 }
 
-int vip_shard_run(vip_shard_t h, uint8_t* d_slab, uint8_t* d_out, size_t out_pitch, void* stream) {
-    if (const int rc = check_run(h, d_slab, d_out, out_pitch)) return rc;
+// vip_shard_run (events null: graph mode applies) and vip_shard_run_timed
+static int run_frame(vip_shard_t h, uint8_t* slab, uint8_t* out, size_t out_pitch, hipStream_t s,
+                     void* const* events) {
+    if (const int rc = check_run(h, slab, out, out_pitch)) return rc;
     DeviceGuard guard;
-    VIP_HIP_TRY(hipSetDevice(h->device));
-    const hipStream_t s = (hipStream_t)stream;
+    VIP_TRY(hipSetDevice(h->device));
     // the null stream cannot be captured; the first exchange connects the peers directly
-    if (h->graph && h->warm && s != nullptr) return run_graph(h, d_slab, d_out, out_pitch, s);
-    const int rc = enqueue_run(h, d_slab, d_out, out_pitch, s, nullptr);
+    if (!events && h->graph && h->warm && s != nullptr) return run_graph(h, slab, out, out_pitch, s);
+    const int rc = enqueue_run(h, slab, out, out_pitch, s, events);
     if (!rc) h->warm = true;
     return rc;
+}
+
+int vip_shard_run(vip_shard_t h, uint8_t* d_slab, uint8_t* d_out, size_t out_pitch, void* stream) {
+    return run_frame(h, d_slab, d_out, out_pitch, (hipStream_t)stream, nullptr);
 }
 
 int vip_shard_run_timed(vip_shard_t h, uint8_t* d_slab, uint8_t* d_out, size_t out_pitch, void* stream,
                         void* const* events) {
     if (!events) return VIP_ERR_INVALID_ARGUMENT;
-    if (const int rc = check_run(h, d_slab, d_out, out_pitch)) return rc;
-    DeviceGuard guard;
-    VIP_HIP_TRY(hipSetDevice(h->device));
-    const int rc = enqueue_run(h, d_slab, d_out, out_pitch, (hipStream_t)stream, events);
-    if (!rc) h->warm = true;
-    return rc;
+    return run_frame(h, d_slab, d_out, out_pitch, (hipStream_t)stream, events);
 }
 
 int vip_shard_run_group(vip_shard_t* hs, int n, uint8_t* const* slabs, uint8_t* const* outs, size_t out_pitch,
@@ -770,14 +770,14 @@ int vip_shard_run_group(vip_shard_t* hs, int n, uint8_t* const* slabs, uint8_t* 
     auto st = [&](int i) { return (hipStream_t)streams[i]; };
     // own rows written -> the exchange may read them
     for (int i = 0; i < n; ++i) {
-        VIP_HIP_TRY(hipSetDevice(hs[i]->device));
-        VIP_HIP_TRY(hipEventRecord(hs[i]->ev_in, st(i)));
+        VIP_TRY(hipSetDevice(hs[i]->device));
+        VIP_TRY(hipEventRecord(hs[i]->ev_in, st(i)));
     }
     if (n > 1 && hs[0]->r > 0) {
         if (rccl) {
             for (int i = 0; i < n; ++i) {
-                VIP_HIP_TRY(hipSetDevice(hs[i]->device));
-                VIP_HIP_TRY(hipStreamWaitEvent(hs[i]->comm, hs[i]->ev_in, 0));
+                VIP_TRY(hipSetDevice(hs[i]->device));
+                VIP_TRY(hipStreamWaitEvent(hs[i]->comm, hs[i]->ev_in, 0));
             }
             if (const ncclResult_t e = ncclGroupStart()) return comm_fail(e, "ncclGroupStart");
             int rc = 0;
@@ -788,41 +788,34 @@ int vip_shard_run_group(vip_shard_t* hs, int n, uint8_t* const* slabs, uint8_t* 
             const int rc2 = group_end(hs, n);
             if (rc || rc2) return rc ? rc : rc2;
             for (int i = 0; i < n; ++i) {
-                VIP_HIP_TRY(hipSetDevice(hs[i]->device));
-                VIP_HIP_TRY(hipEventRecord(hs[i]->ev_x, hs[i]->comm));
+                VIP_TRY(hipSetDevice(hs[i]->device));
+                VIP_TRY(hipEventRecord(hs[i]->ev_x, hs[i]->comm));
             }
         } else {
             // LOCAL: every slab on one device; shard 0's stream carries all the copies
             const hipStream_t c = hs[0]->comm;
-            for (int i = 0; i < n; ++i) VIP_HIP_TRY(hipStreamWaitEvent(c, hs[i]->ev_in, 0));
+            for (int i = 0; i < n; ++i) VIP_TRY(hipStreamWaitEvent(c, hs[i]->ev_in, 0));
             for (int i = 0; i < n; ++i) {
                 const vip_shard_s* h = hs[i];
                 const size_t bytes = (size_t)h->r * h->pitch();
                 if (i > 0)  // own top rows -> the halo below of shard i - 1
-                    VIP_HIP_TRY(hipMemcpyAsync(slabs[i - 1] + (size_t)(hs[i - 1]->r + hs[i - 1]->own) * h->pitch(),
+                    VIP_TRY(hipMemcpyAsync(slabs[i - 1] + (size_t)(hs[i - 1]->r + hs[i - 1]->own) * h->pitch(),
                                                slabs[i] + (size_t)h->r * h->pitch(), bytes, hipMemcpyDeviceToDevice, c));
                 if (i < n - 1)  // own bottom rows -> the halo above of shard i + 1
-                    VIP_HIP_TRY(hipMemcpyAsync(slabs[i + 1], slabs[i] + (size_t)h->own * h->pitch(), bytes,
+                    VIP_TRY(hipMemcpyAsync(slabs[i + 1], slabs[i] + (size_t)h->own * h->pitch(), bytes,
                                                hipMemcpyDeviceToDevice, c));
             }
-            VIP_HIP_TRY(hipEventRecord(hs[0]->ev_x, c));  // shard 0's event covers the group
+            VIP_TRY(hipEventRecord(hs[0]->ev_x, c));  // shard 0's event covers the group
         }
         for (int i = 0; i < n; ++i) {
-            VIP_HIP_TRY(hipSetDevice(hs[i]->device));
+            VIP_TRY(hipSetDevice(hs[i]->device));
             const hipEvent_t x = rccl ? hs[i]->ev_x : hs[0]->ev_x;
-            if (!hs[i]->split) {
-                VIP_HIP_TRY(hipStreamWaitEvent(st(i), x, 0));
-                if (const int rc = filter_rows(hs[i], slabs[i], outs[i], out_pitch, 0, hs[i]->own, st(i))) return rc;
-                continue;
-            }
-            if (const int rc = interior(hs[i], slabs[i], outs[i], out_pitch, st(i))) return rc;
-            VIP_HIP_TRY(hipStreamWaitEvent(st(i), x, 0));
-            if (const int rc = edges(hs[i], slabs[i], outs[i], out_pitch, st(i))) return rc;
+            VIP_TRY(after_halos(hs[i], Frames{1, &slabs[i], &outs[i], out_pitch}, st(i), x, nullptr));
         }
         return 0;
     }
     for (int i = 0; i < n; ++i) {  // one shard or no halo: nothing to exchange
-        VIP_HIP_TRY(hipSetDevice(hs[i]->device));
+        VIP_TRY(hipSetDevice(hs[i]->device));
         if (const int rc = filter_rows(hs[i], slabs[i], outs[i], out_pitch, 0, hs[i]->own, st(i))) return rc;
     }
     return 0;

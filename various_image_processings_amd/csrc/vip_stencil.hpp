@@ -1,5 +1,5 @@
-// Tile geometry and kernel arguments shared by the bilateral, joint-bilateral and
-// adaptive-bilateral kernels (gfx950).
+// Tile and tap machinery shared by the bilateral, joint-bilateral and adaptive-bilateral kernels
+// (gfx950). Kernel arguments and the host side of a launch: vip_launch.hpp.
 //
 // Layout in LDS (one workgroup per CU):
 //   [0, 96 KiB)      colour LUT, 768 entries x 32 interleaved copies (word d*32 + c)
@@ -16,21 +16,11 @@
 #include <type_traits>
 #include <utility>
 
-#include "vip_common.hpp"
+#include "vip_exact.hpp"
+#include "vip_launch.hpp"
 
 namespace vip {
 
-constexpr int kMaxRadius = 15;            // ksize <= 31 (BASELINE C5 uses ksize 31)
-constexpr int kWsStride = kMaxRadius + 1; // spatial weights stored as ws[|ky|][|kx|]
-constexpr int kP = 8;                     // outputs per thread
-constexpr int kTW = 16 * kP;              // tile width in pixels
-constexpr int kLdsBudget = 160 * 1024;
-// joint kernel: folded tables behind a saturating address (SatLut) up to this radius. 7 and 8
-// work with 16-copy tables (sat_fold_copies), bit-exact, but measured slower than the
-// 768 x 16 LUT those radii keep: texture JBF R = 7 186.6 -> 207.8 us, R = 8 242.0 -> 274.7
-// (profiles/r06_jbf_fold16_ab.txt)
-constexpr int kSatMaxR = 6;
-constexpr int kFoldEntries = 32;  // the handle's folded tables hold d < 32 (zeros past the colour LUT's end)
 // Largest distance the folded SatLut stores. A larger DZ (51 at R = 4, with 64-entry
 // tables) means fewer saturated lanes and fewer 2-way conflicts on copy 31's bank, but
 // measured no faster: C4 frame 674.8 -> 678.9 us (profiles/r03_sat_variants.txt).
@@ -82,113 +72,7 @@ static_assert(SatLut<6, 0>::DZ >= 25 && SatLut<8, 0, disc_r2_count(8), kSatFoldD
                   SatLut<7, 0, disc_r2_count(7), kSatFoldDz, 32>::DZ < 25,
               "folded tables reach the texture JBF's zero point (d = 25) with sat_fold_copies");
 
-// Frames one launch of the plain bilateral / adaptive kernels may filter (the
-// *_run_rows_batch entry points; a shard's B frames per RCCL group, vip_shard_run_batch).
-constexpr int kMaxBatchFrames = 6;
-// Radii whose plain / adaptive kernels have a multi-frame form (the small-slab radii; a
-// batch of larger radii launches frame by frame)
-constexpr int kBatchMaxRadius = 8;
-
-struct StencilArgs {
-    const uint8_t* src;
-    const uint8_t* guide;  // == src for the plain filters
-    uint8_t* dst;
-    long long src_pitch, guide_pitch, dst_pitch;
-    int width;
-    int out_rows;          // output rows to produce
-    int src_row0;          // source row of output row 0
-    int row_lo, row_hi;    // neighbour rows clamp to [row_lo, row_hi)
-    int tiles_x;
-    int tiles_total;       // tiles_x * tiles_y (persistent workgroups stride over them)
-    int aligned;           // src/guide base and pitch are 4-byte aligned -> dword tile loads
-    int dst_aligned;       // dst base and pitch are 8-byte aligned -> qword stores
-    const float* color;    // colour LUT in device memory
-    int lut_nonzero;       // entries [lut_nonzero, end) of the colour LUT are exactly 0
-    const float* fold;     // or null: [disc_r2_count(R)][kFoldEntries] = RN(ws(r^2) * colour[d])
-    int inflight;          // host only: frames in flight on this device (the small-frame tiling's model)
-    // Multi-frame launch: frame f < nframes reads fsrc[f] and writes fdst[f] (fsrc[0] == src,
-    // fdst[0] == dst; same geometry and pitches); launch tile t is tile t - f * tiles_frame of
-    // frame f, so the persistent workgroups run straight from one frame's tiles into the
-    // next one's (one prologue, the next tile's loads under the current one's taps).
-    int nframes;
-    int tiles_frame;       // tiles per frame (set by the launcher)
-    int free_cus;          // host only: persistent workgroups leave this many CUs to concurrent work
-    // Last-round split (multi-frame kernels, plan_tail): launch tiles [tail_full, tiles_total)
-    // run in the last round as 2^tail_shift pieces each, a piece being a run of the tile's
-    // waves; tail_full == tiles_total and tail_shift == 0 when the rounds come out even.
-    int tail_full, tail_shift;
-    const uint8_t* fsrc[kMaxBatchFrames];
-    uint8_t* fdst[kMaxBatchFrames];
-    float ws[kWsStride * kWsStride];  // spatial LUT, |ky|-major, in the kernarg segment (scalar loads)
-};
-
-// Runtime-radius kernel (vip_stencil_rt.hip): radius 0 and the radii above the
-// templated set, up to the reference's largest (bilateral ksize 65).
-constexpr int kRtMaxRadius = 32;
-
-struct RtArgs {
-    const uint8_t* src;
-    const uint8_t* guide;  // == src for the plain filters
-    uint8_t* dst;
-    long long src_pitch, guide_pitch, dst_pitch;
-    int width, out_rows, src_row0, row_lo, row_hi;  // as StencilArgs
-    int aligned, dst_aligned;
-    const float* color;    // colour LUT (768 or 1536 entries)
-    const float* wsrow;    // [2R+1][wst]: ws(kx, ky) at [ky + R][kx + ra], 0 outside the disc
-    const int* hw;         // [R+1]: disc half-width of row |ky|
-    int R, wst, ra;
-    int L, S, tiles_x;     // set by the launcher
-};
-int launch_stencil_rt(const RtArgs& a, bool joint, bool adaptive, bool fma, hipStream_t stream);
-int stencil_rt_max_radius(bool joint, bool adaptive);
-
-// One workgroup per CU of the current device (the 96 KiB LUT fills most of the CU's
-// LDS), each striding over tiles; fewer blocks than CUs when the frame has fewer tiles.
-inline int device_cus() {
-    static std::atomic<int> cus_by_dev[64];  // CU count per device, 0 = not queried yet
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-    int cus = cus_by_dev[dev & 63].load(std::memory_order_relaxed);
-    if (cus == 0) {
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-            cus = 256;
-        cus_by_dev[dev & 63].store(cus, std::memory_order_relaxed);
-    }
-    return cus;
-}
-
-// free_cus: CUs the launch leaves to concurrent work (StencilArgs::free_cus)
-inline int persistent_blocks(int tiles, int free_cus = 0) {
-    int cus = device_cus() - (free_cus > 0 ? free_cus : 0);
-    cus = cus > 0 ? cus : 1;
-    return tiles < cus ? tiles : cus;
-}
-
 constexpr int lut_words(bool adaptive) { return adaptive ? 1536 * 16 : 768 * 32; }
-
-// A persistent launch of T tiles on B workgroups runs ceil(T / B) rounds; when the last
-// holds k = T mod B tiles, B - k workgroups idle through it while k run a whole tile each
-// (a C2 slab batch at 8 GPUs: 1,530 tiles on 248 workgroups, 6.17 rounds run as 7). The
-// last round's tiles are cut into m = 2^s pieces of WAVES / m waves each, the largest m
-// with k * m <= B, so that k * m workgroups share them; a piece's workgroup still loads
-// the whole tile plane (the apron rows its waves read) and its other waves skip the taps.
-// m divides WAVES (a 12-wave tile is cut in 2 or 4, never 8). Returns s (0: no cut).
-constexpr int tail_shift(int tiles, int blocks, int waves) {
-    if (blocks <= 0 || tiles % blocks == 0) return 0;
-    const long long k = tiles % blocks;
-    int s = 0;
-    while (waves % (2 << s) == 0 && (k << (s + 1)) <= blocks) ++s;
-    return s;
-}
-static_assert(tail_shift(1530, 248, 16) == 2, "C2 slab batch at 8 GPUs: 42 tiles in 4 pieces");
-static_assert(tail_shift(1530, 255, 16) == 0 && tail_shift(100, 100, 16) == 0, "even rounds: no cut");
-static_assert(tail_shift(7 + 2 * 256, 256, 16) == 4 && tail_shift(7 + 2 * 256, 256, 12) == 2, "pieces divide WAVES");
-static_assert(tail_shift(200 + 256, 256, 16) == 0, "k > blocks / 2: whole tiles");
-inline void plan_tail(StencilArgs& a, int blocks, int waves) {
-    const int s = tail_shift(a.tiles_total, blocks, waves);
-    a.tail_full = s ? a.tiles_total - a.tiles_total % blocks : a.tiles_total;
-    a.tail_shift = s;
-}
 
 // Tile filtered by a persistent workgroup at `slot` (= blockIdx.x + k * gridDim.x, round
 // k). In full rounds each XCD (workgroups are dispatched round-robin over the 8 XCDs,
@@ -221,23 +105,19 @@ struct Geom {
     static constexpr int GROUPS = (TW + 2 * L) / 4;          // 4-pixel groups per tile row
 };
 
-// Largest wave count (<= MAXW: 16, 12, 8 or 4) whose LUT (LUTW words) + plane(s) fit
-// the CU's LDS.
-template <int R, int PLANES, int MAXW = 16, int LUTW = lut_words(false), int P = kP, int TPR = 16>
-constexpr int pick_waves() {
-    constexpr int cand[4] = {16, 12, 8, 4};
-    for (int w : cand) {
-        if (w > MAXW) continue;
-        const long long bytes =
-            4LL * LUTW + 4LL * PLANES * (w * Geom<R, P, TPR>::RPW + 2 * R) * Geom<R, P, TPR>::S;
-        if (bytes <= kLdsBudget) return w;
-    }
-    return 0;
-}
-
+// LDS bytes of a WAVES-wave workgroup: the LUT (LUTW words) and the tile plane(s).
 template <int R, int WAVES, int PLANES, int LUTW = lut_words(false), int P = kP, int TPR = 16>
 constexpr int lds_bytes() {
     return 4 * LUTW + 4 * PLANES * (WAVES * Geom<R, P, TPR>::RPW + 2 * R) * Geom<R, P, TPR>::S;
+}
+
+// Largest wave count (<= MAXW: 16, 12, 8 or 4) whose lds_bytes fit the CU's LDS.
+template <int R, int PLANES, int MAXW = 16, int LUTW = lut_words(false), int P = kP, int TPR = 16>
+constexpr int pick_waves() {
+    if (MAXW >= 16 && lds_bytes<R, 16, PLANES, LUTW, P, TPR>() <= kLdsBudget) return 16;
+    if (MAXW >= 12 && lds_bytes<R, 12, PLANES, LUTW, P, TPR>() <= kLdsBudget) return 12;
+    if (MAXW >= 8 && lds_bytes<R, 8, PLANES, LUTW, P, TPR>() <= kLdsBudget) return 8;
+    return MAXW >= 4 && lds_bytes<R, 4, PLANES, LUTW, P, TPR>() <= kLdsBudget ? 4 : 0;
 }
 
 // Calls f(std::integral_constant<int, HW>) for the runtime circle half-width hw.
@@ -308,16 +188,6 @@ __device__ __forceinline__ void win_sum(const uint32_t (&x)[N + K - 1], uint32_t
         s = s + x[j + K - 1] - x[j - 1];
         o[j] = s;
     }
-}
-
-// Correctly rounded (float)s / d for an integer box sum s and the constant d = k^2
-// (or 3): q0 = s*rd, one fma residual, one fma correction. Equal to the IEEE quotient
-// for every s in [0, k^2 * 255], k <= 31 -- checked exhaustively in
-// tests/test_oracle.py::test_constant_division_is_exact (rd = RN(1/d)).
-__device__ __forceinline__ float div_exact(uint32_t s, float d, float rd) {
-    const float f = (float)s;
-    const float q0 = f * rd;
-    return __builtin_fmaf(__builtin_fmaf(-q0, d, f), rd, q0);
 }
 
 // Register-staged prefetch of one tile plane: source rows
@@ -440,13 +310,6 @@ __device__ __forceinline__ uint32_t sat_addr(uint32_t d, uint32_t s, uint32_t bi
     uint32_t r;
     __asm__("v_mad_legacy_u16 %0, %1, %2, %3 clamp" : "=v"(r) : "v"(d), "s"(s), "v"(bias));
     return r;
-}
-
-template <int NT, int ENTRIES, int COPIES>
-__device__ __forceinline__ void stage_lut(uint32_t* lut, const float* color) {
-    LutStage<NT, ENTRIES, COPIES> s;
-    s.load(color);
-    s.store(lut);
 }
 
 // Neighbour words of one tile row, columns [4*C0, 4*C0 + 4*NC), read from LDS in
@@ -590,93 +453,6 @@ __device__ __forceinline__ void row_taps(const uint32_t* gplane, const uint32_t*
     }
 }
 
-// RN(sqrt(x)) for x = 0 or x in [1, 2^24) (the texture gradient's integer sums of
-// squares): the hardware v_sqrt_f32 result s and one neighbour check each way -- the
-// refinement LLVM's correctly rounded sqrtf expansion applies, without its denormal
-// scaling and special-value handling, which these arguments never need. 9 VALU
-// instead of 17; microbench/div_check.hip verifies it against sqrtf for EVERY integer
-// in [0, 2^20) (the gradient sums stay below 6 * 255^2 = 390150).
-__device__ __forceinline__ float sqrt_int_exact(float x) {
-    const float s = __builtin_amdgcn_sqrtf(x);
-    const float sm = __uint_as_float(__float_as_uint(s) - 1u);
-    const float s1 = __builtin_fmaf(-sm, s, x) <= 0.f ? sm : s;
-    const float sp = __uint_as_float(__float_as_uint(s) + 1u);
-    return __builtin_fmaf(-sp, s, x) > 0.f ? sp : s1;
-}
-
-// 2^(j/64), j = 0..63, correctly rounded to double (staged into LDS by the kernels that
-// call exp_tab_f32; internal linkage, one copy per translation unit).
-static __constant__ double kExp2Tab64[64] = {
-#include "vip_exp_tab64.inc"
-};
-
-// (float)exp((double)x) for float x in [0, 32) -- the texture guide's alpha argument
-// sigma_alpha * (rtv - rtv_min) lies in [0, 255 / (5 ksize)] -- in 14 double ops:
-// x = (k/64) ln2 + r with |r| <= ln2/128 (two-part Cody-Waite; k < 2^12, so k * HI is
-// exact), exp(r) - 1 by its degree-5 Taylor polynomial (truncation < 2^-54), times
-// 2^(k mod 64 / 64) from `etab` (kExp2Tab64 in LDS) and 2^(k / 64). microbench/div_check
-// compares it with (float)exp((double)x) for EVERY float in [0, 32).
-__device__ __forceinline__ float exp_tab_f32(float xf, const double* etab) {
-    const double x = (double)xf;
-    const double kd = __builtin_rint(x * 0x1.71547652b82fep+6);  // 64 / ln2
-    const int k = (int)kd;
-    double r = __builtin_fma(-kd, 0x1.62e42fefa3000p-7, x);       // ln2/64, 12 low bits clear
-    r = __builtin_fma(-kd, 0x1.3de6af278ece6p-48, r);             // ln2/64 - HI
-    double q = __builtin_fma(r, 1.0 / 120, 1.0 / 24);
-    q = __builtin_fma(r, q, 1.0 / 6);
-    q = __builtin_fma(r, q, 0.5);
-    const double p = __builtin_fma(r * r, q, r);                  // exp(r) - 1
-    const double t = etab[k & 63];
-    return (float)__builtin_ldexp(__builtin_fma(t, p, t), k >> 6);
-}
-
-// clampi((int)v, 0, 255) written into byte `sel` of `word`: floor (the int conversion's
-// truncation for v >= 0, and below 0 either way) then v_cvt_pk_u8_f32, whose float->u8
-// conversion saturates (an integral input, so its rounding is moot) and packs in the same
-// instruction. microbench/div_check compares it with the clamp for every float |v| < 2048.
-__device__ __forceinline__ uint32_t pack_u8_clamped(float v, uint32_t sel, uint32_t word) {
-    return __builtin_amdgcn_cvt_pk_u8_f32(__builtin_floorf(v), sel, word);
-}
-
-// RN(1/k) for k in [1, 2^38): hardware rcp (1 ulp) + one Newton step. Verified
-// exhaustively over every float of that range by microbench/div_check.hip.
-__device__ __forceinline__ float recip_exact(float k) {
-    const float y0 = __builtin_amdgcn_rcpf(k);
-    return __builtin_fmaf(__builtin_fmaf(-k, y0, 1.0f), y0, y0);
-}
-
-// (float)(n / d) with the IEEE double quotient: the texture guide stage's rtv (CUDA profile,
-// src/bilateral_texture_filter_impl.cu:99-101), n = (double)num in [0, 2^18), d =
-// (double)msum + 1e-9 in [1e-9, 2^20): no scaling is ever needed. Two Newton steps from
-// v_rcp_f64 give r = 1/d to within a few 2^-53 (the first two steps of the compiler's own
-// f64 division), so q = RN(n r) is within 4 double ulps of n/d, and RN_f(q) equals
-// RN_f(RN_d(n/d)) unless n/d lies within that distance of a float rounding midpoint --
-// which q's 29 low mantissa bits show (midpoint: 2^28). Those lanes (about 2^-23 of them)
-// take the IEEE division. 7 f64 ops + 3 integer ops against the division's 11 f64 ops.
-// microbench/div_check compares it with (float)(n / d) on 2^30 inputs, half of them at
-// midpoints. The guide stage itself keeps the IEEE division (exact and measured 0.4 % slower
-// per C4 frame there); div_check is its only caller.
-__device__ __forceinline__ float rtv_quotient(double n, double d) {
-    const double r0 = __builtin_amdgcn_rcp(d);
-    double e = __builtin_fma(-d, r0, 1.0);
-    double r = __builtin_fma(r0, e, r0);
-    e = __builtin_fma(-d, r, 1.0);
-    r = __builtin_fma(r, e, r);
-    const double q = n * r;
-    const uint32_t lo = (uint32_t)__builtin_bit_cast(unsigned long long, q);
-    if (__builtin_expect(((lo & 0x1fffffffu) - (0x10000000u - 64u)) < 128u, 0)) return (float)(n / d);
-    return (float)q;
-}
-
-// RN(s / k) given y = RN(1/k) (Markstein): q0 = RN(s y) is within 1 ulp of s/k, the
-// residual s - k q0 is exact under fma, and one correction rounds correctly. Needs
-// no over/underflow: s in [0, 255 k], k in [1, 1024). Cross-checked on 2^30 random
-// and near-midpoint quotients by microbench/div_check.hip.
-__device__ __forceinline__ float div_by_sumk(float s, float k, float y) {
-    const float q0 = s * y;
-    return __builtin_fmaf(__builtin_fmaf(-k, q0, s), y, q0);
-}
-
 // dst = u8(sum_c / sumk + 0.5f) for the P outputs, packed as RGBX words. RCP: the
 // window holds its centre tap with weight exactly 1 (bilateral, joint), so sumk is in
 // [1, 1024) and the three divides share one exact reciprocal; the adaptive filter's
@@ -754,6 +530,8 @@ template <bool MULTI>
 __device__ __forceinline__ uint8_t* frame_dst(const StencilArgs& a, int item) {
     if constexpr (!MULTI) return a.dst;
     __asm__ volatile("" : "+s"(item));  // recompute here, not from the tile's start
+    // frame_tile's loop again: calling frame_tile<true> here moves the multi-frame kernels'
+    // register allocation (their assembly is not the same)
     int mt = item_tile<MULTI>(a, item), f = 0;
     while (mt >= a.tiles_frame && a.tiles_frame > 0 && f < kMaxBatchFrames - 1) {
         mt -= a.tiles_frame;

@@ -25,6 +25,7 @@
 //   * adaptive: the k x k box sums (the window mean, src/adaptive_bilateral_filter_impl.cu:
 //     79-93) are per-thread sliding row sums over the plane, exact integers; the mean is
 //     the IEEE quotient by k^2 as in the reference.
+#include "vip_launch.hpp"
 #include "vip_stencil.hpp"
 
 namespace vip {
@@ -268,9 +269,8 @@ __global__ __launch_bounds__(kRtWaves * 64) void stencil_rt_kernel(const RtArgs 
 
 template <int COPIES, bool JOINT, bool FMA, bool ADAPTIVE>
 static int launch_rt_c(const RtArgs& a, int lds, hipStream_t stream) {
-    auto kern = stencil_rt_kernel<COPIES, JOINT, FMA, ADAPTIVE>;
-    static std::atomic<unsigned long long> attr_devs{0};
-    if (const int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), kLdsBudget, attr_devs)) return rc;
+    constexpr auto kern = stencil_rt_kernel<COPIES, JOINT, FMA, ADAPTIVE>;
+    if (const int rc = ensure_lds<kern>(kLdsBudget)) return rc;
     note_launch(reinterpret_cast<const void*>(kern));
     const int tiles_y = (a.out_rows + kRtWaves * 4 - 1) / (kRtWaves * 4);
     const long long tiles = (long long)a.tiles_x * tiles_y;
@@ -311,12 +311,6 @@ static int launch_rt(RtArgs a, bool joint, bool adaptive, hipStream_t stream) {
 
 int launch_stencil_rt(const RtArgs& a, bool joint, bool adaptive, bool fma, hipStream_t stream) {
     return fma ? launch_rt<true>(a, joint, adaptive, stream) : launch_rt<false>(a, joint, adaptive, stream);
-}
-
-int stencil_rt_max_radius(bool joint, bool adaptive) {
-    for (int R = kRtMaxRadius; R >= 0; --R)
-        if (rt_lds_bytes(R, joint, adaptive, joint ? 16 : (adaptive ? 16 : 32))) return R;
-    return -1;
 }
 
 }  // namespace vip

@@ -9,6 +9,8 @@
 //   mRTV         : (imax - imin) * mmax / ((double)msum + 1e-9) in double
 //   guide        : exp evaluated as (float)exp(double) (correctly rounded expf),
 //                  g = int(fmaf(alpha, B[argmin], (1 - alpha) * B) + 0.5f)
+#include "vip_exact.hpp"
+#include "vip_launch.hpp"
 #include "vip_stencil.hpp"
 
 namespace vip {
@@ -798,9 +800,8 @@ static int launch_gf(const uint8_t* img, uint8_t* guide, int width, int lo, int 
     using G = GfGeom<R>;
     constexpr int LDS = 4 * G::WORDS_ALL;
     static_assert(LDS <= kLdsBudget, "fused guide tile does not fit LDS");
-    auto kern = texture_guide_fused_kernel<R, CPP>;
-    static std::atomic<unsigned long long> attr_devs{0};
-    if (const int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), LDS, attr_devs)) return rc;
+    constexpr auto kern = texture_guide_fused_kernel<R, CPP>;
+    if (const int rc = ensure_lds<kern>(LDS)) return rc;
     note_launch(reinterpret_cast<const void*>(kern));
     if (gy1 <= gy0) return 0;
     dim3 grid((width + G::TW - 1) / G::TW, (gy1 - gy0 + G::TH - 1) / G::TH);
@@ -971,8 +972,8 @@ __global__ __launch_bounds__(kFuNT) void texture_iteration_fused_kernel(const St
 int launch_texture_iteration_fused(const StencilArgs& a, int ksize, bool cpp, hipStream_t stream) {
     if (ksize != 2 * kFuR + 1) return VIP_ERR_UNSUPPORTED_KSIZE;
     auto kern = cpp ? texture_iteration_fused_kernel<true> : texture_iteration_fused_kernel<false>;
-    static std::atomic<unsigned long long> attr_devs[2];
-    if (const int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), kFuLds, attr_devs[cpp ? 1 : 0]))
+    if (const int rc = cpp ? ensure_lds<texture_iteration_fused_kernel<true>>(kFuLds)
+                           : ensure_lds<texture_iteration_fused_kernel<false>>(kFuLds))
         return rc;
     note_launch(reinterpret_cast<const void*>(kern));
     StencilArgs args = a;
