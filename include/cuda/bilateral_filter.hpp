@@ -27,6 +27,17 @@ public:
     void joint_bilateral_filter(const std::uint8_t* const d_src, const std::uint8_t* const d_guide,
                                 std::uint8_t* const d_dst, void* stream) const;
 
+    // Additive one-channel (8-bit gray) forms, no reference counterpart (include/vip.h
+    // vip_bilateral_run_c1): d_src and d_dst are dense width x height bytes; d_guide is dense gray
+    // (guide_channels 1) or interleaved 3-channel (guide_channels 3). Blocking, and with a
+    // stream non-blocking, as the 3-channel forms above.
+    void bilateral_filter_c1(const std::uint8_t* const d_src, std::uint8_t* const d_dst) const;
+    void joint_bilateral_filter_c1(const std::uint8_t* const d_src, const std::uint8_t* const d_guide,
+                                   const int guide_channels, std::uint8_t* const d_dst) const;
+    void bilateral_filter_c1(const std::uint8_t* const d_src, std::uint8_t* const d_dst, void* stream) const;
+    void joint_bilateral_filter_c1(const std::uint8_t* const d_src, const std::uint8_t* const d_guide,
+                                   const int guide_channels, std::uint8_t* const d_dst, void* stream) const;
+
 protected:
     class Impl;  // defined in bilateral_filter_impl.cuh (test drivers reach it through impl_)
     std::unique_ptr<Impl> impl_;

@@ -25,6 +25,14 @@ public:
     void joint_bilateral_filter(const std::uint8_t* const d_src, const std::uint8_t* const d_guide,
                                 std::uint8_t* const d_dst, void* stream) const;
 
+    // one-channel forms (include/cuda/bilateral_filter.hpp)
+    void bilateral_filter_c1(const std::uint8_t* const d_src, std::uint8_t* const d_dst) const;
+    void joint_bilateral_filter_c1(const std::uint8_t* const d_src, const std::uint8_t* const d_guide,
+                                   const int guide_channels, std::uint8_t* const d_dst) const;
+    void bilateral_filter_c1(const std::uint8_t* const d_src, std::uint8_t* const d_dst, void* stream) const;
+    void joint_bilateral_filter_c1(const std::uint8_t* const d_src, const std::uint8_t* const d_guide,
+                                   const int guide_channels, std::uint8_t* const d_dst, void* stream) const;
+
     vip_bilateral_t handle() const { return handle_; }
 
 private:

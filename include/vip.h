@@ -4,7 +4,8 @@
  * Drop-in boundary for the reference's include/cuda/ headers' API
  * (yuyuyu-bot/various_image_processings). Plain pointers and sizes only; every
  * image pointer is a DEVICE pointer to dense interleaved 8-bit 3-channel data
- * (or f32 where stated). `pitch` arguments are row strides in bytes; the
+ * (or f32 where stated; the *_c1 entry points take 8-bit 1-channel images).
+ * `pitch` arguments are row strides in bytes; the
  * reference API has no pitch, so its wrappers pass width*channels*sizeof(T).
  * `stream` is a hipStream_t (NULL = the legacy default stream). Every run
  * function is asynchronous on `stream`: the C++ wrappers in include/cuda/ add
@@ -151,6 +152,34 @@ int vip_bilateral_run_rows(vip_bilateral_t h, const uint8_t* d_src, size_t src_p
 int vip_bilateral_run_rows_batch(vip_bilateral_t h, int n, const uint8_t* const* d_srcs, size_t src_pitch,
                                  uint8_t* const* d_dsts, size_t dst_pitch, int out_rows, int src_row0, int row_lo,
                                  int row_hi, int free_cus, void* stream);
+/* ---- single-channel (8-bit gray) forms (no reference counterpart). d_src and d_dst are one
+ * byte per pixel; the handle is the same vip_bilateral_t, with its spatial LUT and its
+ * 768-entry colour LUT. Per tap in row-major order over the k x k square, replicate border:
+ *   w = ws[ky,kx] * wc[d];  s += g_n * w (fused in the CUDA profile);  sumk += w;
+ *   dst = u8(s / sumk + 0.5f)
+ * with d = |g_n - g_c| (plain), |G_n - G_c| (guide_channels 1: a gray guide G; only the
+ * first 256 LUT entries are reached) or |dB| + |dG| + |dR| (guide_channels 3: an interleaved
+ * 3-channel guide). Each result is, bit for bit, channel 0 of the 3-channel filter on the
+ * frame (g, 0, 0) (with the guide (G, 0, 0) for a gray guide), and what OpenCV's 8UC1
+ * bilateral weighs by. Plain ksize 1..65 odd, joint 1..47 odd (VIP_ERR_UNSUPPORTED_KSIZE for
+ * a joint call on a larger handle). Any base address and pitch work for d_src, d_guide and
+ * d_dst: the kernels use dword loads / word stores only where the addresses allow, and
+ * never write a byte of d_dst at column >= width or row >= out_rows (row padding stays the
+ * caller's). One launch per call, no device allocation, no intermediate 3-channel buffer.
+ * VIP_ERR_INVALID_ARGUMENT: null handle or pointer, a bad band, guide_channels not 1 or 3
+ * with a guide; VIP_ERR_ALIASING: d_dst equals d_src or d_guide. The gray kernels honour
+ * vip_set_stencil_path as the 3-channel ones do (AUTO: radius-specialised vip::gray_kernel
+ * for radius 1..15, vip::gray_rt_kernel for 0 and 16..32; RUNTIME: gray_rt_kernel always);
+ * vip_bilateral_set_waves / _set_wide / _set_frames_in_flight do not apply to them. */
+int vip_bilateral_run_c1(vip_bilateral_t h, const uint8_t* d_src, size_t src_pitch, uint8_t* d_dst, size_t dst_pitch,
+                         void* stream);
+int vip_joint_bilateral_run_c1(vip_bilateral_t h, const uint8_t* d_src, size_t src_pitch, const uint8_t* d_guide,
+                               size_t guide_pitch, int guide_channels, uint8_t* d_dst, size_t dst_pitch,
+                               void* stream);
+/* Row band, as vip_bilateral_run_rows; d_guide NULL: plain (guide_channels is then ignored) */
+int vip_bilateral_run_rows_c1(vip_bilateral_t h, const uint8_t* d_src, size_t src_pitch, const uint8_t* d_guide,
+                              size_t guide_pitch, int guide_channels, uint8_t* d_dst, size_t dst_pitch, int out_rows,
+                              int src_row0, int row_lo, int row_hi, void* stream);
 /* Tuning knob, process-wide (no reference counterpart): waves per workgroup of the plain
  * bilateral kernel for radius <= 8. 0 (default) = chosen per launch from the frame's
  * tile count (small frames take 8 or 4 waves and smaller tiles so more CUs work);

@@ -9,6 +9,12 @@
 //                                       (sample/bilateral_filter/main.cpp:14-17)
 //   vip_filter joint     IN GUIDE OUT [ksize=9] [sigma_space=10] [sigma_color=30]
 //                                       (CudaBilateralFilter::joint_bilateral_filter)
+//   vip_filter gray      IN OUT [ksize=9] [sigma_space=10] [sigma_color=30]
+//                                       (one-channel bilateral_filter_c1; IN is a gray file,
+//                                       OUT is written with one channel)
+//   vip_filter joint-gray IN GUIDE OUT [ksize=9] [sigma_space=10] [sigma_color=30]
+//                                       (joint_bilateral_filter_c1; GUIDE is a gray or a
+//                                       colour file)
 //   vip_filter adaptive  IN OUT [ksize=9] [sigma_space=10] [sigma_color=30]
 //                                       (sample/adaptive_bilateral_filter/main.cpp:15-18)
 //   vip_filter texture   IN OUT [ksize=9] [nitr=3]
@@ -43,6 +49,8 @@ static int usage() {
     std::fprintf(stderr,
                  "[Usage] vip_filter bilateral IN OUT [ksize] [sigma_space] [sigma_color]\n"
                  "        vip_filter joint IN GUIDE OUT [ksize] [sigma_space] [sigma_color]\n"
+                 "        vip_filter gray IN OUT [ksize] [sigma_space] [sigma_color]\n"
+                 "        vip_filter joint-gray IN GUIDE OUT [ksize] [sigma_space] [sigma_color]\n"
                  "        vip_filter adaptive IN OUT [ksize] [sigma_space] [sigma_color]\n"
                  "        vip_filter texture IN OUT [ksize] [nitr]\n"
                  "        vip_filter gradient IN OUT\n"
@@ -82,7 +90,8 @@ int main(int argc, char** argv) {
     }
     if (args.size() < 3) return usage();
     const std::string mode = args[0];
-    const bool joint = mode == "joint";
+    const bool gray = mode == "gray" || mode == "joint-gray";
+    const bool joint = mode == "joint" || mode == "joint-gray";
     const size_t np = joint ? 4 : 3;  // index of the first numeric parameter
     if (args.size() < np) return usage();
     auto int_arg = [&](size_t i, int def) { return args.size() > i ? std::stoi(args[i]) : def; };
@@ -91,14 +100,18 @@ int main(int argc, char** argv) {
 
     vip_io::Image in, guide;
     try {
-        in = vip_io::read_image(args[1]);
-        if (joint) guide = vip_io::read_image(args[2]);
+        in = gray ? vip_io::read_image_native(args[1]) : vip_io::read_image(args[1]);
+        if (joint) guide = gray ? vip_io::read_image_native(args[2]) : vip_io::read_image(args[2]);
     } catch (const std::exception& e) {
         std::fprintf(stderr, "Failed to load: %s\n", e.what());
         return 1;
     }
     if (joint && (guide.width != in.width || guide.height != in.height)) {
         std::fprintf(stderr, "guide size %dx%d != image size %dx%d\n", guide.width, guide.height, in.width, in.height);
+        return 1;
+    }
+    if (gray && in.channels != 1) {
+        std::fprintf(stderr, "%s: not a gray (one-channel) file\n", args[1].c_str());
         return 1;
     }
     const int W = in.width, H = in.height;
@@ -111,6 +124,23 @@ int main(int argc, char** argv) {
     try {
         if (mode == "convert") {
             out = in;
+        } else if (gray) {
+            out.channels = 1;
+            out.data.resize((size_t)W * H);
+            DeviceImage<std::uint8_t> d_src(W, H, 1), d_dst(W, H, 1);
+            d_src.upload(in.data.data());
+            CudaBilateralFilter filter(W, H, int_arg(np, 9), flt_arg(np + 1, 10.f), flt_arg(np + 2, 30.f));
+            if (joint) {
+                DeviceImage<std::uint8_t> d_guide(W, H, guide.channels);
+                d_guide.upload(guide.data.data());
+                run_timed("joint bilateral filter (gray)", repeat, [&] {
+                    filter.joint_bilateral_filter_c1(d_src.get(), d_guide.get(), guide.channels, d_dst.get());
+                });
+            } else {
+                run_timed("bilateral filter (gray)", repeat, [&] { filter.bilateral_filter_c1(d_src.get(), d_dst.get()); });
+            }
+            if (!device_ok()) return 2;
+            d_dst.download(out.data.data());
         } else if (mode == "bilateral" || joint || mode == "adaptive" || mode == "texture") {
             DeviceImage<std::uint8_t> d_src(W, H, 3), d_dst(W, H, 3);
             d_src.upload(in.data.data());

@@ -33,6 +33,7 @@ namespace vip_io {
 struct Image {
     int width = 0, height = 0, channels = 0;  // channels 3 (BGR) or 1 (gray)
     std::vector<std::uint8_t> data;           // dense, row stride width * channels
+    int file_channels = 0;                    // read_image: 1 when the file stored gray samples, else 3
 };
 
 inline std::vector<std::uint8_t> read_file(const std::string& path) {
@@ -220,6 +221,7 @@ inline Image decode(const std::vector<std::uint8_t>& f) {
     img.width = W;
     img.height = H;
     img.channels = 3;
+    img.file_channels = ctype != 3 && spp <= 2 ? 1 : 3;
     img.data.resize((size_t)W * H * 3);
     for (size_t i = 0; i < (size_t)W * H; ++i) {
         const std::uint8_t* s = px.data() + i * spp;
@@ -341,6 +343,7 @@ inline Image decode(const std::vector<std::uint8_t>& f) {
     img.width = (int)W;
     img.height = (int)H;
     img.channels = 3;
+    img.file_channels = C;
     img.data.resize((size_t)W * H * 3);
     for (size_t i = 0; i < (size_t)W * H; ++i) {
         std::uint8_t s[3];
@@ -382,6 +385,18 @@ inline Image read_image(const std::string& path) {
     if (f.size() >= 8 && std::memcmp(f.data(), png::kSig, 8) == 0) return png::decode(f);
     if (f.size() >= 2 && f[0] == 'P' && (f[1] == '5' || f[1] == '6')) return pnm::decode(f);
     throw std::runtime_error(path + ": not a PNG, PPM or PGM file");
+}
+
+// As cv::imread(path, cv::IMREAD_UNCHANGED) for 8-bit output: a file of gray samples (gray or
+// gray+alpha PNG, PGM) keeps one channel instead of being widened; any other file is BGR.
+inline Image read_image_native(const std::string& path) {
+    Image img = read_image(path);
+    if (img.file_channels != 1) return img;
+    const size_t n = (size_t)img.width * img.height;
+    for (size_t i = 0; i < n; ++i) img.data[i] = img.data[3 * i];
+    img.data.resize(n);
+    img.channels = 1;
+    return img;
 }
 
 // .png -> PNG, .ppm / .pgm / .pnm -> binary PNM; img is BGR (3 channels) or gray (1).

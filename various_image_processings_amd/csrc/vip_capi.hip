@@ -588,6 +588,38 @@ int vip_bilateral_run_rows(vip_bilateral_t h, const uint8_t* d_src, size_t src_p
                     (hipStream_t)stream);
 }
 
+// ---- single-channel forms (vip_gray.hip): the same band, handle and tables; guide_channels 0
+// plain, 1 or 3 joint
+int vip_bilateral_run_rows_c1(vip_bilateral_t h, const uint8_t* d_src, size_t src_pitch, const uint8_t* d_guide,
+                              size_t guide_pitch, int guide_channels, uint8_t* d_dst, size_t dst_pitch, int out_rows,
+                              int src_row0, int row_lo, int row_hi, void* stream) {
+    if (!h) return VIP_ERR_INVALID_ARGUMENT;
+    const RowBand b{d_src, src_pitch, d_guide, guide_pitch, d_dst, dst_pitch, out_rows, src_row0, row_lo, row_hi};
+    if (const int rc = check_band(h->height, b)) return rc;
+    const bool joint = d_guide != nullptr;
+    if (joint && guide_channels != 1 && guide_channels != 3) return VIP_ERR_INVALID_ARGUMENT;
+    if (joint && h->ksize > kMaxKsizeJoint) return VIP_ERR_UNSUPPORTED_KSIZE;
+    const int gch = joint ? guide_channels : 0;
+    const bool fma = h->numerics == VIP_NUMERICS_CUDA;
+    if (use_runtime_kernel(h->radius)) return launch_gray_rt(rt_args(*h, b), gch, fma, (hipStream_t)stream);
+    return launch_gray(h->radius, gch, fma, stencil_args(*h, b), (hipStream_t)stream);
+}
+
+int vip_bilateral_run_c1(vip_bilateral_t h, const uint8_t* d_src, size_t src_pitch, uint8_t* d_dst, size_t dst_pitch,
+                         void* stream) {
+    if (!h) return VIP_ERR_INVALID_ARGUMENT;
+    return vip_bilateral_run_rows_c1(h, d_src, src_pitch, nullptr, 0, 0, d_dst, dst_pitch, h->height, 0, 0, h->height,
+                                     stream);
+}
+
+int vip_joint_bilateral_run_c1(vip_bilateral_t h, const uint8_t* d_src, size_t src_pitch, const uint8_t* d_guide,
+                               size_t guide_pitch, int guide_channels, uint8_t* d_dst, size_t dst_pitch,
+                               void* stream) {
+    if (!h || !d_guide) return VIP_ERR_INVALID_ARGUMENT;
+    return vip_bilateral_run_rows_c1(h, d_src, src_pitch, d_guide, guide_pitch, guide_channels, d_dst, dst_pitch,
+                                     h->height, 0, 0, h->height, stream);
+}
+
 // The frames of a *_run_rows_batch call, or a run of them
 struct Batch {
     int n;

@@ -59,6 +59,26 @@ void CudaBilateralFilter::Impl::joint_bilateral_filter(const std::uint8_t* const
     VIP_REPORT(vip_joint_bilateral_run(handle_, d_src, pitch, d_guide, pitch, d_dst, pitch, stream));
 }
 
+void CudaBilateralFilter::Impl::bilateral_filter_c1(const std::uint8_t* const d_src, std::uint8_t* const d_dst) const {
+    bilateral_filter_c1(d_src, d_dst, nullptr);
+}
+void CudaBilateralFilter::Impl::bilateral_filter_c1(const std::uint8_t* const d_src, std::uint8_t* const d_dst,
+                                                    void* stream) const {
+    VIP_REPORT(vip_bilateral_run_c1(handle_, d_src, (size_t)width_, d_dst, (size_t)width_, stream));
+}
+void CudaBilateralFilter::Impl::joint_bilateral_filter_c1(const std::uint8_t* const d_src,
+                                                          const std::uint8_t* const d_guide, const int guide_channels,
+                                                          std::uint8_t* const d_dst) const {
+    joint_bilateral_filter_c1(d_src, d_guide, guide_channels, d_dst, nullptr);
+}
+void CudaBilateralFilter::Impl::joint_bilateral_filter_c1(const std::uint8_t* const d_src,
+                                                          const std::uint8_t* const d_guide, const int guide_channels,
+                                                          std::uint8_t* const d_dst, void* stream) const {
+    const size_t pitch = (size_t)width_;
+    VIP_REPORT(vip_joint_bilateral_run_c1(handle_, d_src, pitch, d_guide, pitch * (size_t)(guide_channels == 3 ? 3 : 1),
+                                          guide_channels, d_dst, pitch, stream));
+}
+
 CudaBilateralFilter::CudaBilateralFilter(const int width, const int height, const int ksize, const float sigma_space,
                                          const float sigma_color)
     : impl_(std::make_unique<Impl>(width, height, ksize, sigma_space, sigma_color)) {}
@@ -83,6 +103,25 @@ void CudaBilateralFilter::bilateral_filter(const std::uint8_t* const d_src, std:
 void CudaBilateralFilter::joint_bilateral_filter(const std::uint8_t* const d_src, const std::uint8_t* const d_guide,
                                                  std::uint8_t* const d_dst, void* stream) const {
     impl_->joint_bilateral_filter(d_src, d_guide, d_dst, stream);
+}
+
+void CudaBilateralFilter::bilateral_filter_c1(const std::uint8_t* const d_src, std::uint8_t* const d_dst) const {
+    impl_->bilateral_filter_c1(d_src, d_dst);
+    VIP_REPORT(vip_device_synchronize());
+}
+void CudaBilateralFilter::joint_bilateral_filter_c1(const std::uint8_t* const d_src, const std::uint8_t* const d_guide,
+                                                    const int guide_channels, std::uint8_t* const d_dst) const {
+    impl_->joint_bilateral_filter_c1(d_src, d_guide, guide_channels, d_dst);
+    VIP_REPORT(vip_device_synchronize());
+}
+void CudaBilateralFilter::bilateral_filter_c1(const std::uint8_t* const d_src, std::uint8_t* const d_dst,
+                                              void* stream) const {
+    impl_->bilateral_filter_c1(d_src, d_dst, stream);
+}
+void CudaBilateralFilter::joint_bilateral_filter_c1(const std::uint8_t* const d_src, const std::uint8_t* const d_guide,
+                                                    const int guide_channels, std::uint8_t* const d_dst,
+                                                    void* stream) const {
+    impl_->joint_bilateral_filter_c1(d_src, d_guide, guide_channels, d_dst, stream);
 }
 
 // ------------------------------------------------------------ CudaAdaptiveBilateralFilter

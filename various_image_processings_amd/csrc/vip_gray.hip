@@ -1,0 +1,515 @@
+// Single-channel (8-bit gray) bilateral and joint-bilateral kernels for gfx950 (MI355X).
+//
+// Definition (include/vip.h, vip_bilateral_run_c1): per output pixel and per tap in row-major
+// order over the k x k square, w = ws[ky,kx] * wc[d], s += g_n * w, sumk += w,
+// dst = u8(s / sumk + 0.5f), replicate border; d = |g_n - g_c| (plain), |G_n - G_c| (gray
+// guide G) or |dB| + |dG| + |dR| (3-channel guide). That is channel 0 of the 3-channel
+// filter on the frame (g, 0, 0), so the 3-channel oracle is this one's oracle.
+//
+// One LDS word per pixel in every form, so one ds_read_b128 feeds 4 neighbours and
+// v_sad_u8 yields the colour distance in one instruction:
+//   plain        word = g                       d = sad(word, centre)
+//   gray guide   word = G | g << 8              d = sad(word & 0xff, centre)
+//   RGB guide    word = B | G << 8 | R << 16 | g << 24   d = sad(word & 0xffffff, centre)
+// The mask and the u8 -> float conversion of g are per neighbour word, shared by the
+// thread's outputs; a tap is v_sad_u8, v_lshl_add (LUT address), ds_read_b32, v_mul (spatial
+// weight from an SGPR), v_fmac, v_add: 5 VALU against the 3-channel kernel's 7 (counted in the
+// radius-7 kernel's assembly: 1192 of each per thread and tile, 5.6 VALU per tap overall).
+// The colour LUT is the handle's 768-entry table; the plain and gray-guide forms reach only
+// its first 256 entries and hold 256 x 32 interleaved copies (32 KiB), the RGB-guide form
+// 768 x 32 (96 KiB).
+//
+// Two kernels, as for the 3-channel filters:
+//   gray_kernel<R, GUIDE, FMA>     radius 1..15 a template argument; persistent 16-wave
+//       workgroups over 128 x 64 tiles, 8 outputs per thread, every tile row straight-line
+//       code with a compile-time disc half-width (vip_stencil.hpp: Geom, for_each_row,
+//       RowStream), the next tile's HBM reads in flight under the current tile's taps.
+//   gray_rt_kernel<GUIDE, FMA>     radius a kernel argument (0 and 16..32, or every radius
+//       under VIP_PATH_RUNTIME); one workgroup per 64 x 64 tile, 4 outputs per thread, taps
+//       in blocks of 4 with exact zero weights outside the disc (as vip_stencil_rt.hip).
+// Both numerics profiles (FMA: explicit __builtin_fmaf; otherwise mul + add, the build
+// has -ffp-contract=off) are instantiated here.
+#include "vip_launch.hpp"
+#include "vip_stencil.hpp"
+
+namespace vip {
+
+// GUIDE: 0 plain, 1 gray guide, 3 interleaved 3-channel guide
+template <int GUIDE>
+struct GrayWord {
+    static_assert(GUIDE == 0 || GUIDE == 1 || GUIDE == 3, "guide channels");
+    static constexpr uint32_t MASK = GUIDE == 3 ? 0xffffffu : 0xffu;   // the guide's bytes
+    static constexpr int SHIFT = GUIDE == 3 ? 24 : (GUIDE == 1 ? 8 : 0);  // the source's byte
+    static constexpr int ENTRIES = GUIDE == 3 ? 768 : 256;              // colour-LUT entries d can reach
+    __device__ __forceinline__ static uint32_t guide(uint32_t w) { return GUIDE == 0 ? w : (w & MASK); }
+    __device__ __forceinline__ static float source(uint32_t w) { return (float)((w >> SHIFT) & 0xffu); }
+};
+constexpr int kGrayCopies = 32;
+
+// 4 gray pixels of one image row from column x (columns clamped to the image), pixel k in
+// byte k: one dword load when the group is interior and the row is dword aligned.
+__device__ __forceinline__ uint32_t load_gray4(const uint8_t* row, int x, int width, int aligned) {
+    if (aligned && x >= 0 && x + 3 < width) return *reinterpret_cast<const uint32_t*>(row + x);
+    return (uint32_t)row[clampi(x + 0, 0, width - 1)] | ((uint32_t)row[clampi(x + 1, 0, width - 1)] << 8) |
+           ((uint32_t)row[clampi(x + 2, 0, width - 1)] << 16) | ((uint32_t)row[clampi(x + 3, 0, width - 1)] << 24);
+}
+
+// One 4-pixel group as loaded from HBM (the source dword and the guide's 1 or 3 dwords),
+// and as the 4 plane words it becomes.
+template <int GUIDE>
+struct GrayGroup {
+    uint32_t s, g0, g1, g2;
+
+    __device__ __forceinline__ void load(const uint8_t* src, long long src_pitch, const uint8_t* guide,
+                                         long long guide_pitch, int sy, int x, int width, int aligned) {
+        s = load_gray4(src + (long long)sy * src_pitch, x, width, aligned);
+        g0 = g1 = g2 = 0u;
+        if constexpr (GUIDE == 1) g0 = load_gray4(guide + (long long)sy * guide_pitch, x, width, aligned);
+        if constexpr (GUIDE == 3) {
+            const uint8_t* row = guide + (long long)sy * guide_pitch;
+            if (aligned && x >= 0 && x + 3 < width) {
+                const uint32_t* w = reinterpret_cast<const uint32_t*>(row + 3 * x);
+                g0 = w[0];
+                g1 = w[1];
+                g2 = w[2];
+            } else {
+                const uint32_t q0 = load_rgb(row, clampi(x + 0, 0, width - 1));
+                const uint32_t q1 = load_rgb(row, clampi(x + 1, 0, width - 1));
+                const uint32_t q2 = load_rgb(row, clampi(x + 2, 0, width - 1));
+                const uint32_t q3 = load_rgb(row, clampi(x + 3, 0, width - 1));
+                g0 = q0 | (q1 << 24);
+                g1 = (q1 >> 8) | (q2 << 16);
+                g2 = (q2 >> 16) | (q3 << 8);
+            }
+        }
+    }
+
+    __device__ __forceinline__ uint4 words() const {
+        uint4 r;
+        if constexpr (GUIDE == 0) {
+            r.x = s & 0xffu;
+            r.y = (s >> 8) & 0xffu;
+            r.z = (s >> 16) & 0xffu;
+            r.w = s >> 24;
+        } else if constexpr (GUIDE == 1) {
+            r.x = (g0 & 0xffu) | ((s & 0xffu) << 8);
+            r.y = ((g0 >> 8) & 0xffu) | (s & 0xff00u);
+            r.z = ((g0 >> 16) & 0xffu) | ((s >> 8) & 0xff00u);
+            r.w = (g0 >> 24) | ((s >> 16) & 0xff00u);
+        } else {
+            const uint4 u = unpack_rgb4(g0, g1, g2);
+            r.x = u.x | (s << 24);
+            r.y = u.y | ((s & 0xff00u) << 16);
+            r.z = u.z | ((s & 0xff0000u) << 8);
+            r.w = u.w | (s & 0xff000000u);
+        }
+        return r;
+    }
+};
+
+// Register-staged prefetch of one tile plane (TilePrefetch's gray form): issue() starts the
+// HBM loads of source rows [ty0 + src_row0 - R, +ROWS) x columns [tx0 - L, tx0 + TW + L),
+// rows clamped to [row_lo, row_hi), columns to [0, width); commit() writes the plane words.
+template <int R, int ROWS, int NT, int P, int GUIDE>
+struct GrayPrefetch {
+    using G = Geom<R, P, 16>;
+    static constexpr int NG = ROWS * G::GROUPS;
+    static constexpr int K = (NG + NT - 1) / NT;
+    GrayGroup<GUIDE> raw[K];
+
+    __device__ __forceinline__ void issue(const StencilArgs& a, int tx0, int ty0) {
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            const int g = (int)threadIdx.x + k * NT;
+            if (NG % NT != 0 && k == K - 1 && g >= NG) continue;
+            const int r = g / G::GROUPS;
+            const int gc = g - r * G::GROUPS;
+            const int sy = clampi(ty0 + a.src_row0 - R + r, a.row_lo, a.row_hi - 1);
+            raw[k].load(a.src, a.src_pitch, a.guide, a.guide_pitch, sy, tx0 - G::L + 4 * gc, a.width, a.aligned);
+        }
+    }
+    __device__ __forceinline__ void commit(uint32_t* plane) const {
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            const int g = (int)threadIdx.x + k * NT;
+            if (NG % NT != 0 && k == K - 1 && g >= NG) continue;
+            const int r = g / G::GROUPS;
+            const int gc = g - r * G::GROUPS;
+            *reinterpret_cast<uint4*>(plane + r * G::S + 4 * gc) = raw[k].words();
+        }
+    }
+};
+
+// Write P gray outputs of row oy from column x: one word store where dst allows it
+// (dst_aligned: base and pitch are P-byte aligned) and the outputs are all inside the row,
+// single bytes otherwise; never a byte at column >= width or row >= out_rows.
+template <int P, class A>
+__device__ __forceinline__ void store_gray(const A& a, int oy, int x, const uint32_t (&o)[P]) {
+    static_assert(P == 4 || P == 8, "outputs per thread");
+    if (oy >= a.out_rows || x >= a.width) return;
+    uint8_t* p = a.dst + (long long)oy * a.dst_pitch + x;
+    if (a.dst_aligned && x + P <= a.width) {
+        const uint32_t w0 = o[0] | (o[1] << 8) | (o[2] << 16) | (o[3] << 24);
+        if constexpr (P == 8) {
+            const uint32_t w1 = o[4] | (o[5] << 8) | (o[6] << 16) | (o[7] << 24);
+            *reinterpret_cast<uint2*>(p) = make_uint2(w0, w1);
+        } else {
+            *reinterpret_cast<uint32_t*>(p) = w0;
+        }
+        return;
+    }
+#pragma unroll
+    for (int i = 0; i < P; ++i)
+        if (x + i < a.width) p[i] = (uint8_t)o[i];
+}
+
+// The tap loop of one tile row (row_taps' one-accumulator form): neighbour column j serves
+// output i at kx = j - L - i; per output the taps run in ascending kx.
+template <int HW, int L, int C0, int NC, bool FMA, int P, int GUIDE>
+__device__ __forceinline__ void gray_row_taps(const uint32_t* plane, int row_off, const float (&wsv)[HW + 1],
+                                              const char* lut, uint32_t lane4, const uint32_t (&ctr)[P],
+                                              float (&s)[P], float (&sk)[P]) {
+    using W = GrayWord<GUIDE>;
+    constexpr int D = kPipeDepth, NB = D + 1;
+    constexpr int J0 = L - HW, J1 = L + P - 1 + HW;
+    constexpr int LA = D + kRowLookahead;
+    static_assert(J0 >= 4 * C0 && J1 < 4 * (C0 + NC), "row chunk range");
+    auto chunk = [](int j) constexpr { return (j - 4 * C0) >> 2; };
+    constexpr int PRE = chunk(J0 + LA < J1 ? J0 + LA : J1);
+    RowStream<C0, NC, false> row(plane, plane, row_off);
+#pragma unroll
+    for (int q = 0; q <= PRE; ++q) row.load(q);
+    float wc[NB][P], nf[NB];
+    auto issue = [&](int j) {
+        const uint32_t w = row.guide(j - 4 * C0);
+        const uint32_t g = W::guide(w);
+        const int b = (j - J0) % NB;
+        nf[b] = W::source(w);
+#pragma unroll
+        for (int i = 0; i < P; ++i) {
+            const int kx = j - L - i;
+            if (kx < -HW || kx > HW) continue;
+            const uint32_t d = __builtin_amdgcn_sad_u8(g, ctr[i], 0u);
+            wc[b][i] = *reinterpret_cast<const float*>(lut + ((d << 7) | lane4));
+        }
+    };
+#pragma unroll
+    for (int j = J0; j < J0 + D && j <= J1; ++j) issue(j);
+#pragma unroll
+    for (int j = J0; j <= J1; ++j) {
+        if (j + LA <= J1 && ((j + LA) & 3) == 0 && chunk(j + LA) > PRE) row.load(chunk(j + LA));
+        if (j + D <= J1) issue(j + D);
+        const int b = (j - J0) % NB;
+#pragma unroll
+        for (int i = 0; i < P; ++i) {
+            const int kx = j - L - i;
+            if (kx < -HW || kx > HW) continue;
+            const float w = wc[b][i] * wsv[kx < 0 ? -kx : kx];
+            if constexpr (FMA)
+                s[i] = __builtin_fmaf(nf[b], w, s[i]);
+            else
+                s[i] = s[i] + nf[b] * w;
+            sk[i] = sk[i] + w;
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    }
+}
+
+constexpr int kGrayP = 8, kGrayWaves = 16;
+template <int R, int GUIDE>
+constexpr int gray_lds_bytes() {
+    return 4 * (GrayWord<GUIDE>::ENTRIES * kGrayCopies + (kGrayWaves * 4 + 2 * R) * Geom<R, kGrayP, 16>::S);
+}
+
+template <int R, int GUIDE, bool FMA>
+__global__ __launch_bounds__(kGrayWaves * 64) void gray_kernel(const StencilArgs a) {
+    using W = GrayWord<GUIDE>;
+    constexpr int P = kGrayP, WAVES = kGrayWaves, NT = WAVES * 64;
+    using G = Geom<R, P, 16>;
+    constexpr int TH = WAVES * G::RPW;
+    constexpr int ROWS = TH + 2 * R;
+    static_assert(kGrayCopies == 32, "LUT address: d << 7");
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+    uint32_t* const lut = lds;
+    uint32_t* const plane = lds + W::ENTRIES * kGrayCopies;
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int tx = lane & 15;
+    const int ty = wave * G::RPW + (lane >> 4);
+    const uint32_t lane4 = (uint32_t)(lane & (kGrayCopies - 1)) << 2;  // this lane's LUT copy
+    const char* const lut_bytes = reinterpret_cast<const char*>(lut);
+
+    // persistent: workgroup b filters tiles b, b + grid, ... (xcd_tile's placement)
+    int tile = blockIdx.x;
+    GrayPrefetch<R, ROWS, NT, P, GUIDE> pf;
+    LutStage<NT, W::ENTRIES, kGrayCopies> ls;
+    ls.load(a.color);
+    {
+        const int t = xcd_tile(tile, a.tiles_total);
+        pf.issue(a, (t % a.tiles_x) * G::TW, (t / a.tiles_x) * TH);
+    }
+    ls.store(lut);
+    pf.commit(plane);
+    __syncthreads();
+
+    for (;;) {
+        const int t = xcd_tile(tile, a.tiles_total);
+        const int tx0 = (t % a.tiles_x) * G::TW, ty0 = (t / a.tiles_x) * TH;
+        const int next = tile + (int)gridDim.x;
+        if (next < a.tiles_total) {  // next tile's HBM reads fly under this tile's taps
+            const int n = xcd_tile(next, a.tiles_total);
+            pf.issue(a, (n % a.tiles_x) * G::TW, (n / a.tiles_x) * TH);
+        }
+        if (ty0 + wave * G::RPW < a.out_rows) {  // wave-uniform: skip rows past the band
+            uint32_t ctr[P];
+            {
+                const uint4* c = reinterpret_cast<const uint4*>(plane + (ty + R) * G::S + tx * P + G::L);
+#pragma unroll
+                for (int q = 0; q < P / 4; ++q) {
+                    const uint4 v = c[q];
+                    ctr[4 * q + 0] = W::guide(v.x);
+                    ctr[4 * q + 1] = W::guide(v.y);
+                    ctr[4 * q + 2] = W::guide(v.z);
+                    ctr[4 * q + 3] = W::guide(v.w);
+                }
+            }
+            float s[P], sk[P];
+#pragma unroll
+            for (int i = 0; i < P; ++i) s[i] = sk[i] = 0.f;
+
+            for_each_row<R, true>([&](const int ky, auto hwc) {
+                constexpr int HW = decltype(hwc)::value;
+                const int aky = ky < 0 ? -ky : ky;
+                set_progress_priority((ky + R) * 4 / (2 * R + 1));
+                const int row_off = (ty + R + ky) * G::S + tx * P;
+                const float* const ws = a.ws + aky * kWsStride;
+                constexpr int C0 = (G::L - HW) / 4, C1 = (G::L + P - 1 + HW) / 4;
+                constexpr int NC = C1 - C0 + 1;
+                float wsv[HW + 1];
+#pragma unroll
+                for (int k = 0; k <= HW; ++k) wsv[k] = ws[k];
+                gray_row_taps<HW, G::L, C0, NC, FMA, P, GUIDE>(plane, row_off, wsv, lut_bytes, lane4, ctr, s, sk);
+                // pin the accumulators at the row's end (fence_accumulators)
+#pragma unroll
+                for (int i = 0; i < P; ++i) __asm__ volatile("" : "+v"(s[i]), "+v"(sk[i]));
+            });
+
+            uint32_t o[P];
+#pragma unroll
+            for (int i = 0; i < P; ++i) o[i] = f2u8(s[i] / sk[i] + 0.5f);
+            store_gray(a, ty0 + ty, tx0 + tx * P, o);
+        }
+        if (next >= a.tiles_total) break;
+        __syncthreads();  // every wave is done reading this tile
+        pf.commit(plane);
+        __syncthreads();
+        tile = next;
+    }
+}
+
+template <int R, int GUIDE, bool FMA>
+static int launch_gray_r(const StencilArgs& a, hipStream_t stream) {
+    using G = Geom<R, kGrayP, 16>;
+    constexpr int LDS = gray_lds_bytes<R, GUIDE>();
+    static_assert(LDS <= kLdsBudget, "tile does not fit LDS");
+    constexpr auto kern = gray_kernel<R, GUIDE, FMA>;
+    return launch_persistent<kern, nullptr, LDS, kGrayWaves, G::TW, kGrayWaves * G::RPW, false>(a, false, stream);
+}
+
+template <int GUIDE, bool FMA>
+static int launch_gray_dispatch(int radius, const StencilArgs& a, hipStream_t stream) {
+    switch (radius) {
+#define VIP_CASE(RR) \
+    case RR: return launch_gray_r<RR, GUIDE, FMA>(a, stream);
+        VIP_CASE(1) VIP_CASE(2) VIP_CASE(3) VIP_CASE(4) VIP_CASE(5) VIP_CASE(6) VIP_CASE(7) VIP_CASE(8)
+        VIP_CASE(9) VIP_CASE(10) VIP_CASE(11) VIP_CASE(12) VIP_CASE(13) VIP_CASE(14) VIP_CASE(15)
+#undef VIP_CASE
+        default: return VIP_ERR_UNSUPPORTED_KSIZE;
+    }
+}
+
+int launch_gray(int radius, int guide_channels, bool fma, const StencilArgs& a, hipStream_t s) {
+    switch (guide_channels) {
+        case 0: return fma ? launch_gray_dispatch<0, true>(radius, a, s) : launch_gray_dispatch<0, false>(radius, a, s);
+        case 1: return fma ? launch_gray_dispatch<1, true>(radius, a, s) : launch_gray_dispatch<1, false>(radius, a, s);
+        case 3: return fma ? launch_gray_dispatch<3, true>(radius, a, s) : launch_gray_dispatch<3, false>(radius, a, s);
+        default: return VIP_ERR_INVALID_ARGUMENT;
+    }
+}
+
+// ---------------------------------------------------------------- runtime radius
+constexpr int kGrayRtP = 4;                // outputs per thread
+constexpr int kGrayRtTW = 16 * kGrayRtP;   // tile width in pixels
+constexpr int kGrayRtWaves = 16;           // 64 tile rows
+
+// LDS words of the tile plane: (64 + 2R) rows x S words, + a zeroed pad when the apron is
+// narrower than the one-block over-read of the last row (R = 0 only)
+__host__ __device__ constexpr int gray_rt_plane_words(int R, int L, int S) {
+    return (kGrayRtWaves * 4 + 2 * R) * S + (L < 4 ? 8 : 0);
+}
+// S = 64 or 128: the 16-lane groups of a ds_read_b128 hit disjoint banks
+__host__ __device__ constexpr int gray_rt_stride(int L) { return kGrayRtTW + 2 * L <= 64 ? 64 : 128; }
+
+// 4 consecutive plane words: guide bytes (colour distance) and source floats (sums)
+template <int GUIDE>
+struct GrayRtWin {
+    uint32_t g[4];
+    float c[4];
+    __device__ __forceinline__ void load(const uint32_t* plane, int off) {
+        const uint4 v = *reinterpret_cast<const uint4*>(plane + off);
+        const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            g[k] = GrayWord<GUIDE>::guide(w[k]);
+            c[k] = GrayWord<GUIDE>::source(w[k]);
+        }
+    }
+};
+
+#define kconst __attribute__((address_space(4)))
+
+template <int GUIDE, bool FMA>
+__global__ __launch_bounds__(kGrayRtWaves * 64) void gray_rt_kernel(const RtArgs a) {
+    using W = GrayWord<GUIDE>;
+    constexpr int P = kGrayRtP, NT = kGrayRtWaves * 64, TH = kGrayRtWaves * 4;
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+    const int R = a.R, L = a.L, S = a.S;
+    const int rows = TH + 2 * R;
+    const int pw = gray_rt_plane_words(R, L, S);
+    uint32_t* const plane = lds;
+    uint32_t* const lut = lds + pw;
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int tx = lane & 15;
+    const int ty = wave * 4 + (lane >> 4);
+    const int tile = blockIdx.x;
+    const int tx0 = (tile % a.tiles_x) * kGrayRtTW, ty0 = (tile / a.tiles_x) * TH;
+
+    // colour LUT: word d * 32 + c = color[d]
+    for (int q = tid; q < W::ENTRIES * kGrayCopies / 4; q += NT) {
+        const uint32_t v = __float_as_uint(a.color[q >> 3]);
+        *reinterpret_cast<uint4*>(lut + 4 * q) = make_uint4(v, v, v, v);
+    }
+    // tile plane; columns [TW + 2L, S) and the pad are zeroed: the last tap block of a row
+    // reads up to 4 words past its apron (weight 0), and a zero word's distance to any
+    // centre stays inside the LUT (d <= 255, or 765 with a 3-channel guide)
+    {
+        const int gpr = S / 4, valid = (kGrayRtTW + 2 * L) / 4;
+        for (int q = tid; q < rows * gpr; q += NT) {
+            const int r = q / gpr, gc = q - r * gpr;
+            uint4 w = make_uint4(0u, 0u, 0u, 0u);
+            if (gc < valid) {
+                const int sy = clampi(ty0 + a.src_row0 - R + r, a.row_lo, a.row_hi - 1);
+                GrayGroup<GUIDE> grp;
+                grp.load(a.src, a.src_pitch, a.guide, a.guide_pitch, sy, tx0 - L + 4 * gc, a.width, a.aligned);
+                w = grp.words();
+            }
+            *reinterpret_cast<uint4*>(plane + r * S + 4 * gc) = w;
+        }
+        if (L < 4 && tid < 2) *reinterpret_cast<uint4*>(plane + rows * S + 4 * tid) = make_uint4(0u, 0u, 0u, 0u);
+    }
+    __syncthreads();
+    if (ty0 + wave * 4 >= a.out_rows) return;  // wave-uniform; no barrier follows
+
+    const int xc = L + tx * P;  // plane column of the thread's output 0
+    uint32_t ctr[P];
+    {
+        const uint4 v = *reinterpret_cast<const uint4*>(plane + (ty + R) * S + xc);
+        ctr[0] = W::guide(v.x); ctr[1] = W::guide(v.y); ctr[2] = W::guide(v.z); ctr[3] = W::guide(v.w);
+    }
+    const uint32_t lanec = (uint32_t)(lane & (kGrayCopies - 1)) << 2;
+    const char* const lut_bytes = reinterpret_cast<const char*>(lut);
+
+    float s[P], sk[P];
+#pragma unroll
+    for (int i = 0; i < P; ++i) s[i] = sk[i] = 0.f;
+
+    // 4 taps x 4 outputs: tap t of the block pairs output i with word t + i of cur|nxt
+    auto block = [&](const GrayRtWin<GUIDE>& cur, const GrayRtWin<GUIDE>& nxt, const kconst float* wsb) {
+        const float wsv[4] = {wsb[0], wsb[1], wsb[2], wsb[3]};  // uniform: one scalar load
+        float wc[4][P];
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+#pragma unroll
+            for (int i = 0; i < P; ++i) {
+                const int j = t + i;
+                const uint32_t d = __builtin_amdgcn_sad_u8(j < 4 ? cur.g[j & 3] : nxt.g[j & 3], ctr[i], 0u);
+                wc[t][i] = *reinterpret_cast<const float*>(lut_bytes + ((d << 7) | lanec));
+            }
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+#pragma unroll
+            for (int i = 0; i < P; ++i) {
+                const int j = t + i;
+                const float n = j < 4 ? cur.c[j & 3] : nxt.c[j & 3];
+                const float w = wc[t][i] * wsv[t];
+                if constexpr (FMA)
+                    s[i] = __builtin_fmaf(n, w, s[i]);
+                else
+                    s[i] = s[i] + n * w;
+                sk[i] = sk[i] + w;
+            }
+    };
+
+    for (int ky = -R; ky <= R; ++ky) {
+        const int aky = ky < 0 ? -ky : ky;
+        set_progress_priority((ky + R) * 4 / (2 * R + 1));
+        const int hw = ((const kconst int*)a.hw)[aky];
+        const int k4 = (hw + 3) & ~3;
+        const int nblk = ((hw + k4) >> 2) + 1;  // blocks cover kx = -k4 .. -k4 + 4 nblk - 1 >= hw
+        const kconst float* const wsr = (const kconst float*)a.wsrow + (ky + R) * a.wst + (a.ra - k4);
+        const int off = (ty + R + ky) * S + xc - k4;
+        GrayRtWin<GUIDE> A, B;
+        A.load(plane, off);
+        int b = 0;
+        for (; b + 2 <= nblk; b += 2) {  // two blocks per trip: the windows swap roles
+            B.load(plane, off + 4 * (b + 1));
+            block(A, B, wsr + 4 * b);
+            A.load(plane, off + 4 * (b + 2));
+            block(B, A, wsr + 4 * (b + 1));
+        }
+        if (b < nblk) {
+            B.load(plane, off + 4 * (b + 1));
+            block(A, B, wsr + 4 * b);
+        }
+    }
+
+    uint32_t o[P];
+#pragma unroll
+    for (int i = 0; i < P; ++i) o[i] = f2u8(s[i] / sk[i] + 0.5f);
+    store_gray(a, ty0 + ty, tx0 + tx * P, o);
+}
+
+template <int GUIDE, bool FMA>
+static int launch_gray_rt_g(RtArgs a, hipStream_t stream) {
+    if (a.R < 0 || a.R > kRtMaxRadius) return VIP_ERR_UNSUPPORTED_KSIZE;
+    a.L = round_up(a.R, 4);
+    a.S = gray_rt_stride(a.L);
+    a.tiles_x = (a.width + kGrayRtTW - 1) / kGrayRtTW;
+    const long long lds = 4LL * (gray_rt_plane_words(a.R, a.L, a.S) + GrayWord<GUIDE>::ENTRIES * kGrayCopies);
+    if (lds > kLdsBudget) return VIP_ERR_UNSUPPORTED_KSIZE;
+    constexpr auto kern = gray_rt_kernel<GUIDE, FMA>;
+    if (const int rc = ensure_lds<kern>(kLdsBudget)) return rc;
+    note_launch(reinterpret_cast<const void*>(kern));
+    const int tiles_y = (a.out_rows + kGrayRtWaves * 4 - 1) / (kGrayRtWaves * 4);
+    const long long tiles = (long long)a.tiles_x * tiles_y;
+    if (tiles == 0) return 0;
+    if (tiles > 0x7fffffffLL) return VIP_ERR_INVALID_ARGUMENT;
+    launch(kern, dim3((unsigned)tiles), dim3(kGrayRtWaves * 64), (uint32_t)lds, stream, a);
+    return (int)hipGetLastError();
+}
+
+int launch_gray_rt(const RtArgs& a, int guide_channels, bool fma, hipStream_t s) {
+    switch (guide_channels) {
+        case 0: return fma ? launch_gray_rt_g<0, true>(a, s) : launch_gray_rt_g<0, false>(a, s);
+        case 1: return fma ? launch_gray_rt_g<1, true>(a, s) : launch_gray_rt_g<1, false>(a, s);
+        case 3: return fma ? launch_gray_rt_g<3, true>(a, s) : launch_gray_rt_g<3, false>(a, s);
+        default: return VIP_ERR_INVALID_ARGUMENT;
+    }
+}
+
+}  // namespace vip

@@ -5,7 +5,8 @@ yuyuyu-bot/various_image_processings:
 
 * ``CudaBilateralFilter(width, height, ksize=9, sigma_space=10., sigma_color=30.)``
   with ``bilateral_filter(d_src, d_dst)`` and ``joint_bilateral_filter(d_src, d_guide, d_dst)``
-  (include/cuda/bilateral_filter.hpp:9-24)
+  (include/cuda/bilateral_filter.hpp:9-24), and their one-channel forms ``bilateral_filter_c1(d_src,
+  d_dst)`` / ``joint_bilateral_filter_c1(d_src, d_guide, guide_channels, d_dst)`` (no reference counterpart)
 * ``CudaAdaptiveBilateralFilter(...).execute(d_src, d_dst)`` (adaptive_bilateral_filter.hpp:9-19)
 * ``CudaBilateralTextureFilter(width, height, ksize=9, nitr=3).execute(d_src, d_dst)``
   (bilateral_texture_filter.hpp:9-12)
@@ -200,6 +201,33 @@ class _BilateralImpl(_Handle):
         call("vip_bilateral_run_rows", self._h, _ptr(d_src, p * int(row_hi)), p, g, p, _ptr(d_dst, p * int(out_rows)),
              p, int(out_rows), int(src_row0), int(row_lo), int(row_hi), _stream(stream))
 
+    # single-channel (8-bit gray) forms, include/vip.h vip_bilateral_run_c1: d_src and d_dst are
+    # width * height bytes; the guide is gray (guide_channels 1) or interleaved 3-channel (3)
+    @staticmethod
+    def _guide_channels(guide_channels) -> int:
+        if int(guide_channels) not in (1, 3):
+            raise VipError("vip_joint_bilateral_run_c1", _lib.VIP_ERR_INVALID_ARGUMENT)
+        return int(guide_channels)
+
+    def bilateral_filter_c1(self, d_src, d_dst, stream=None):
+        p, n = self.width, self.width * self.height
+        call("vip_bilateral_run_c1", self._h, _ptr(d_src, n), p, _ptr(d_dst, n), p, _stream(stream))
+
+    def joint_bilateral_filter_c1(self, d_src, d_guide, guide_channels, d_dst, stream=None):
+        p, n, gch = self.width, self.width * self.height, self._guide_channels(guide_channels)
+        call("vip_joint_bilateral_run_c1", self._h, _ptr(d_src, n), p, _ptr(d_guide, n * gch), p * gch, gch,
+             _ptr(d_dst, n), p, _stream(stream))
+
+    def run_rows_c1(self, d_src, d_dst, out_rows, src_row0, row_lo, row_hi, d_guide=None, guide_channels=1,
+                    stream=None):
+        """run_rows for one-channel images (include/vip.h vip_bilateral_run_rows_c1)."""
+        p = self.width
+        gch = 0 if d_guide is None else self._guide_channels(guide_channels)
+        g = None if d_guide is None else _ptr(d_guide, p * gch * int(row_hi))
+        call("vip_bilateral_run_rows_c1", self._h, _ptr(d_src, p * int(row_hi)), p, g, p * gch, gch,
+             _ptr(d_dst, p * int(out_rows)), p, int(out_rows), int(src_row0), int(row_lo), int(row_hi),
+             _stream(stream))
+
     def run_rows_batch(self, d_srcs, d_dsts, out_rows, src_row0, row_lo, row_hi, free_cus=0, stream=None):
         """run_rows over several frames of the same geometry, up to 6 per launch
         (include/vip.h vip_bilateral_run_rows_batch)."""
@@ -229,6 +257,15 @@ class CudaBilateralFilter:
 
     def joint_bilateral_filter(self, d_src, d_guide, d_dst):
         self.impl_.joint_bilateral_filter(d_src, d_guide, d_dst)
+        device_synchronize()
+
+    def bilateral_filter_c1(self, d_src, d_dst):
+        """One-channel form (no reference counterpart; include/vip.h vip_bilateral_run_c1)."""
+        self.impl_.bilateral_filter_c1(d_src, d_dst)
+        device_synchronize()
+
+    def joint_bilateral_filter_c1(self, d_src, d_guide, guide_channels, d_dst):
+        self.impl_.joint_bilateral_filter_c1(d_src, d_guide, guide_channels, d_dst)
         device_synchronize()
 
 
