@@ -1,5 +1,5 @@
 #!/bin/bash
-# Build an experimental R=7 plain-FMA bilateral library variant into /root/repo/variants/<name>.so
+# Build an experimental R=7 plain-FMA bilateral library variant (radii 4, 7, 15) into variants/<name>.so
 # usage: build_variant.sh <name> <extra hipcc flags...>   (e.g. -DVIP_STAMPS for stamp_bench.py; the sources
 # carry no experiment knobs, so any other variant is built from edited sources)
 set -e
@@ -16,5 +16,5 @@ hipcc $F -DVIP_ONLY_R7 -c vip_adaptive.hip -o /tmp/var_$name/am.o
 # the texture, C ABI and C++ API objects of the in-place CMake build (__graft_entry__.build())
 O=../../build/cmake/CMakeFiles
 hipcc --offload-arch=gfx950 -shared -o ../../variants/$name.so /tmp/var_$name/*.o \
-  $(ls $O/vip_{texture,capi,stencil_rt}.dir/various_image_processings_amd/csrc/*.o $O/vip_hip.dir/various_image_processings_amd/csrc/*.o)
+  $(ls $O/vip_{texture,capi,stencil_rt,gray}.dir/various_image_processings_amd/csrc/*.o $O/vip_hip.dir/various_image_processings_amd/csrc/*.o)
 echo built variants/$name.so

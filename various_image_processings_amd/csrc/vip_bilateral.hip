@@ -60,6 +60,14 @@ struct FoldRank {  // table index of tap (|ky|, |kx|)
             for (int x = 0; x <= R; ++x) t[y * (R + 1) + x] = disc_r2_rank(R, x * x + y * y);
     }
 };
+// Largest |i - j| of a thread's outputs i, j whose centre-row weight is formed once and used by
+// both (row_taps SHARE): 18 of the 28 pairs of 8 outputs, all 6 of 4 outputs, at most 6 weights
+// held at once. At this distance the 4K kernels need no more registers than without sharing
+// (VGPRs / spilled: C2's r = 7 108 / 0 as before, C5's r = 15 128 / 5 -> 4, the texture JBF's
+// folded r = 4 128 / 1 -> 127 / 0). All 28 pairs (16 held at once) measured faster still at C2
+// and the JBF but take 6 more VGPRs at C2 and spill in the kernels at the
+// 128-VGPR limit (joint r = 7: 15 -> 20 spilled VGPRs, plain r = 15: 5 -> 11, no gain at C5).
+constexpr int kPairShareDist = 3;
 // The kernel body; MULTI: a multi-frame launch (bilateral_frames_kernel), whose tiles run
 // from one frame into the next (StencilArgs::nframes). The one-frame kernel compiles with
 // MULTI = false, to exactly the code it had before multi-frame launches existed.
@@ -89,6 +97,11 @@ __device__ __forceinline__ void bilateral_body(const StencilArgs& a) {
     const uint32_t lane4 = (uint32_t)(lane & (COPIES - 1)) << 2;  // this lane's LUT copy
     const uint32_t sbias = (uint32_t)SL::B0 + lane4;                // SAT: register bias of the address
     const char* const lut_bytes = reinterpret_cast<const char*>(lut);
+    // The centre tap's weight (kx = ky = 0, d = 0 for every output), once per thread: the
+    // float product the tap formed, ws[0][0] * wc[0], or the folded table's entry (r^2 = 0, d = 0)
+    // (wave-uniform: kept in a scalar register, the taps' v_fma take it as their one scalar operand)
+    const float w0 = __uint_as_float(__builtin_amdgcn_readfirstlane(
+        __float_as_uint(FOLD ? a.fold[disc_r2_rank(R, 0) * kFoldEntries] : a.color[0] * a.ws[0])));
 
     VIP_RT_STAMP(0);
     // persistent: workgroup b filters items b, b + grid, b + 2 grid, ... (item_tile: the
@@ -159,8 +172,15 @@ __device__ __forceinline__ void bilateral_body(const StencilArgs& a) {
                         }
                         return (d << (COPIES == 32 ? 7 : 6)) | lane4;
                     };
-                    row_taps<HW, G::L, C0, NC, FMA, P, JOINT, decltype(widx)&, FOLD, kPipeDepth, SAT>(
-                        gplane, splane, row_off, wsv, lut_bytes, widx, a01, a2k);
+                    // the outputs' own row shares each in-thread pair's weight and takes w0 at
+                    // the centre tap (row_taps SHARE); ky is a constant in the unrolled rows
+                    if (ky == 0)
+                        row_taps<HW, G::L, C0, NC, FMA, P, JOINT, decltype(widx)&, FOLD, kPipeDepth, SAT,
+                                 kPairShareDist>(
+                            gplane, splane, row_off, wsv, lut_bytes, widx, a01, a2k, w0);
+                    else
+                        row_taps<HW, G::L, C0, NC, FMA, P, JOINT, decltype(widx)&, FOLD, kPipeDepth, SAT>(
+                            gplane, splane, row_off, wsv, lut_bytes, widx, a01, a2k);
                     if constexpr (ROW_UNROLL) fence_accumulators(a01, a2k);
             });
 

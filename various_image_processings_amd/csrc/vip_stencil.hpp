@@ -389,11 +389,22 @@ __device__ __forceinline__ void fence_accumulators(f2 (&a01)[P], f2 (&a2k)[P]) {
 // ABS: widx returns an absolute LDS byte address (the kernel's dynamic LDS starts at 0),
 // read through an address-space-3 pointer, so a constant part of it lands in the ds_read
 // immediate instead of a v_add of the LDS base.
+// SHARE >= 0: the row is the outputs' own row (ky = 0) and the weight depends on the two
+// guide words through a symmetric distance only (bilateral, joint; not the adaptive filter's
+// offset distance). Columns L..L+P-1 are then the thread's own outputs: output i meets
+// output j there as tap kx = j - i and j meets i as kx = i - j, the same float
+// ws[|i-j|] * wc[sad(word_i, word_j)]. For |i - j| <= SHARE output j forms it at column
+// L + i (i < j, the earlier column) and output i takes it from a register at column L + j,
+// without sad, address, LUT read and multiply. The weights live at once are the pairs that
+// straddle a column: 16 of the 28 at P = 8 with SHARE = 7, 6 with SHARE = 3 -- the caller
+// picks what its registers hold (kPairShareDist, vip_bilateral.hip). The centre tap
+// (kx = 0, d = 0) takes `w0`, the caller's ws[0][0] * wc[0] (FOLD: the table entry), formed
+// once per thread. Every output still accumulates in ascending kx, so no sum changes.
 template <int HW, int L, int C0, int NC, bool FMA, int P, bool TWO, class WIdx, bool FOLD = false,
-          int D = kPipeDepth, bool ABS = false>
+          int D = kPipeDepth, bool ABS = false, int SHARE = -1>
 __device__ __forceinline__ void row_taps(const uint32_t* gplane, const uint32_t* splane, int row_off,
                                          const float (&wsv)[HW + 1], const char* lut, WIdx&& widx,
-                                         f2 (&a01)[P], f2 (&a2k)[P]) {
+                                         f2 (&a01)[P], f2 (&a2k)[P], [[maybe_unused]] const float w0 = 0.f) {
     constexpr int NB = D + 1;            // ring of in-flight columns
     constexpr int J0 = L - HW;           // first neighbour column relative to the thread's P
     constexpr int J1 = L + P - 1 + HW;   // last
@@ -406,6 +417,10 @@ __device__ __forceinline__ void row_taps(const uint32_t* gplane, const uint32_t*
     for (int q = 0; q <= PRE; ++q) row.load(q);
     float wc[NB][P];
     f2 n01[NB], n21[NB];                 // {b, g} and {r, 1} of the neighbour (source image)
+    // is tap kx at column j one of an in-thread pair whose weight is shared (kx < 0: formed
+    // here and kept, kx > 0: taken from the pair's other output), or the centre tap (w0)?
+    auto own = [](int j, int kx) constexpr { return j >= L && j < L + P && kx >= -SHARE && kx <= SHARE; };
+    [[maybe_unused]] float pw[P][P];     // pw[i][j], i < j: the pair's weight, formed at column L + i
     auto issue = [&](int j) {
         const uint32_t g = row.guide(j - 4 * C0);
         const uint32_t p = row.source(j - 4 * C0);
@@ -418,6 +433,7 @@ __device__ __forceinline__ void row_taps(const uint32_t* gplane, const uint32_t*
         for (int i = 0; i < P; ++i) {
             const int kx = j - L - i;
             if (kx < -HW || kx > HW) continue;
+            if (own(j, kx) && kx >= 0) continue;
             if constexpr (ABS)
                 wc[b][i] = *reinterpret_cast<const __attribute__((address_space(3))) float*>(
                     (size_t)widx(g, n01[b], n21[b], i, kx));
@@ -436,7 +452,15 @@ __device__ __forceinline__ void row_taps(const uint32_t* gplane, const uint32_t*
         for (int i = 0; i < P; ++i) {
             const int kx = j - L - i;
             if (kx < -HW || kx > HW) continue;
-            const float w = FOLD ? wc[b][i] : wc[b][i] * wsv[kx < 0 ? -kx : kx];
+            float w;
+            if (own(j, kx) && kx == 0) {
+                w = w0;
+            } else if (own(j, kx) && kx > 0) {
+                w = pw[i][j - L];
+            } else {
+                w = FOLD ? wc[b][i] : wc[b][i] * wsv[kx < 0 ? -kx : kx];
+                if (own(j, kx)) pw[j - L][i] = w;
+            }
             if constexpr (FMA) {
                 a01[i].x = __builtin_fmaf(n01[b].x, w, a01[i].x);
                 a01[i].y = __builtin_fmaf(n01[b].y, w, a01[i].y);
