@@ -18,6 +18,9 @@ public:
 
     void execute(const std::uint8_t* const d_src, std::uint8_t* const d_dst) const;
     void execute(const std::uint8_t* const d_src, std::uint8_t* const d_dst, void* stream) const;
+    // one-channel form (vip_adaptive_run_c1)
+    void execute_c1(const std::uint8_t* const d_src, std::uint8_t* const d_dst) const;
+    void execute_c1(const std::uint8_t* const d_src, std::uint8_t* const d_dst, void* stream) const;
 
     vip_adaptive_t handle() const { return handle_; }
 

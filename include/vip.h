@@ -216,6 +216,30 @@ int vip_adaptive_run_rows(vip_adaptive_t h, const uint8_t* d_src, size_t src_pit
 int vip_adaptive_run_rows_batch(vip_adaptive_t h, int n, const uint8_t* const* d_srcs, size_t src_pitch,
                                 uint8_t* const* d_dsts, size_t dst_pitch, int out_rows, int src_row0, int row_lo,
                                 int row_hi, int free_cus, void* stream);
+/* ---- single-channel (8-bit gray) form (no reference counterpart). d_src and d_dst are one
+ * byte per pixel; the handle is the same vip_adaptive_t, with its spatial LUT and its colour
+ * LUT, of which one channel reaches only the first 511 entries. Per output pixel, replicate
+ * border, radius = ksize / 2:
+ *   mean = (float)(sum of g over the full k x k square) / (float)(k * k);  o = (float)c - mean
+ *   per tap in row-major order over the k x k square:
+ *     dist = |((float)n - (float)c) - o|;  w = ws[ky,kx] * wc[(int)dist]
+ *     s += n * w (fused in the CUDA profile);  sumk += w
+ *   dst = u8(s / sumk + 0.5f)
+ * dist = |n - 2c + mean| <= 510 for every input. The result is, bit for bit, channel 0 of
+ * vip_adaptive_run on the frame (g, 0, 0): channels 1 and 2 add exact zeros to dist. ksize
+ * 1..63 odd. Any base address and pitch work for d_src and d_dst: the kernels use dword
+ * loads / word stores only where the addresses allow, and never write a byte of d_dst at
+ * column >= width or row >= out_rows (row padding stays the caller's). One launch per call,
+ * no device allocation, no intermediate 3-channel buffer. VIP_ERR_INVALID_ARGUMENT: null
+ * handle or pointer, a bad band; VIP_ERR_ALIASING: d_dst equals d_src. vip_set_stencil_path is
+ * honoured (AUTO: radius-specialised vip::gray_adaptive_kernel for radius 1..15,
+ * vip::gray_adaptive_rt_kernel for 0 and 16..31; RUNTIME: gray_adaptive_rt_kernel always).
+ * There is no multi-frame (batch) form, and the vip_bilateral_set_* knobs do not apply. */
+int vip_adaptive_run_c1(vip_adaptive_t h, const uint8_t* d_src, size_t src_pitch, uint8_t* d_dst, size_t dst_pitch,
+                        void* stream);
+/* Row band, as vip_adaptive_run_rows */
+int vip_adaptive_run_rows_c1(vip_adaptive_t h, const uint8_t* d_src, size_t src_pitch, uint8_t* d_dst,
+                             size_t dst_pitch, int out_rows, int src_row0, int row_lo, int row_hi, void* stream);
 
 /* ---- gradient magnitude: cuda_gradient<T> (include/cuda/gradient.hpp:4-23, src/gradient_impl.cu:90-112) ---- */
 int vip_gradient_u8(const uint8_t* d_src, float* d_dst, int width, int height, int src_ch, int numerics,

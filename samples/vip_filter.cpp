@@ -17,6 +17,9 @@
 //                                       colour file)
 //   vip_filter adaptive  IN OUT [ksize=9] [sigma_space=10] [sigma_color=30]
 //                                       (sample/adaptive_bilateral_filter/main.cpp:15-18)
+//   vip_filter adaptive-gray IN OUT [ksize=9] [sigma_space=10] [sigma_color=30]
+//                                       (one-channel CudaAdaptiveBilateralFilter::execute_c1; IN
+//                                       is a gray file, OUT is written with one channel)
 //   vip_filter texture   IN OUT [ksize=9] [nitr=3]
 //                                       (sample/bilateral_texture_filter/main.cpp:15-17)
 //   vip_filter gradient  IN OUT         (sample/gradient/main.cpp:23-40; OUT is the
@@ -52,6 +55,7 @@ static int usage() {
                  "        vip_filter gray IN OUT [ksize] [sigma_space] [sigma_color]\n"
                  "        vip_filter joint-gray IN GUIDE OUT [ksize] [sigma_space] [sigma_color]\n"
                  "        vip_filter adaptive IN OUT [ksize] [sigma_space] [sigma_color]\n"
+                 "        vip_filter adaptive-gray IN OUT [ksize] [sigma_space] [sigma_color]\n"
                  "        vip_filter texture IN OUT [ksize] [nitr]\n"
                  "        vip_filter gradient IN OUT\n"
                  "        vip_filter convert IN OUT\n"
@@ -90,7 +94,7 @@ int main(int argc, char** argv) {
     }
     if (args.size() < 3) return usage();
     const std::string mode = args[0];
-    const bool gray = mode == "gray" || mode == "joint-gray";
+    const bool gray = mode == "gray" || mode == "joint-gray" || mode == "adaptive-gray";
     const bool joint = mode == "joint" || mode == "joint-gray";
     const size_t np = joint ? 4 : 3;  // index of the first numeric parameter
     if (args.size() < np) return usage();
@@ -129,15 +133,23 @@ int main(int argc, char** argv) {
             out.data.resize((size_t)W * H);
             DeviceImage<std::uint8_t> d_src(W, H, 1), d_dst(W, H, 1);
             d_src.upload(in.data.data());
-            CudaBilateralFilter filter(W, H, int_arg(np, 9), flt_arg(np + 1, 10.f), flt_arg(np + 2, 30.f));
-            if (joint) {
-                DeviceImage<std::uint8_t> d_guide(W, H, guide.channels);
-                d_guide.upload(guide.data.data());
-                run_timed("joint bilateral filter (gray)", repeat, [&] {
-                    filter.joint_bilateral_filter_c1(d_src.get(), d_guide.get(), guide.channels, d_dst.get());
-                });
+            const int ksize = int_arg(np, 9);
+            const float sigma_space = flt_arg(np + 1, 10.f), sigma_color = flt_arg(np + 2, 30.f);
+            if (mode == "adaptive-gray") {
+                CudaAdaptiveBilateralFilter filter(W, H, ksize, sigma_space, sigma_color);
+                run_timed("adaptive bilateral filter (gray)", repeat, [&] { filter.execute_c1(d_src.get(), d_dst.get()); });
             } else {
-                run_timed("bilateral filter (gray)", repeat, [&] { filter.bilateral_filter_c1(d_src.get(), d_dst.get()); });
+                CudaBilateralFilter filter(W, H, ksize, sigma_space, sigma_color);
+                if (joint) {
+                    DeviceImage<std::uint8_t> d_guide(W, H, guide.channels);
+                    d_guide.upload(guide.data.data());
+                    run_timed("joint bilateral filter (gray)", repeat, [&] {
+                        filter.joint_bilateral_filter_c1(d_src.get(), d_guide.get(), guide.channels, d_dst.get());
+                    });
+                } else {
+                    run_timed("bilateral filter (gray)", repeat,
+                              [&] { filter.bilateral_filter_c1(d_src.get(), d_dst.get()); });
+                }
             }
             if (!device_ok()) return 2;
             d_dst.download(out.data.data());

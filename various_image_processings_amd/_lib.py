@@ -84,6 +84,9 @@ SIGNATURES = {
     "vip_adaptive_run_rows_batch": (
         _c_int, [_c_void_p, _c_int, ctypes.POINTER(_c_void_p), _c_size_t, ctypes.POINTER(_c_void_p), _c_size_t,
                  _c_int, _c_int, _c_int, _c_int, _c_int, _c_void_p]),
+    "vip_adaptive_run_c1": (_c_int, [_c_void_p, _c_void_p, _c_size_t, _c_void_p, _c_size_t, _c_void_p]),
+    "vip_adaptive_run_rows_c1": (
+        _c_int, [_c_void_p, _c_void_p, _c_size_t, _c_void_p, _c_size_t, _c_int, _c_int, _c_int, _c_int, _c_void_p]),
     "vip_gradient_u8": (_c_int, [_c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_int, _c_void_p]),
     "vip_gradient_f32": (_c_int, [_c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_int, _c_void_p]),
     "vip_texture_create": (_c_int, [ctypes.POINTER(_c_void_p), _c_int, _c_int, _c_int, _c_int, _c_int]),

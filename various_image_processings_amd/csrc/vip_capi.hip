@@ -729,6 +729,23 @@ int vip_adaptive_run(vip_adaptive_t h, const uint8_t* d_src, size_t src_pitch, u
     return vip_adaptive_run_rows(h, d_src, src_pitch, d_dst, dst_pitch, h->height, 0, 0, h->height, stream);
 }
 
+// ---- single-channel form (vip_gray_adaptive.hip): the same band, handle and tables
+int vip_adaptive_run_rows_c1(vip_adaptive_t h, const uint8_t* d_src, size_t src_pitch, uint8_t* d_dst,
+                             size_t dst_pitch, int out_rows, int src_row0, int row_lo, int row_hi, void* stream) {
+    if (!h) return VIP_ERR_INVALID_ARGUMENT;
+    const RowBand b{d_src, src_pitch, nullptr, 0, d_dst, dst_pitch, out_rows, src_row0, row_lo, row_hi};
+    if (const int rc = check_band(h->height, b)) return rc;
+    const bool fma = h->numerics == VIP_NUMERICS_CUDA;
+    if (use_runtime_kernel(h->radius)) return launch_gray_adaptive_rt(rt_args(*h, b), fma, (hipStream_t)stream);
+    return launch_gray_adaptive(h->radius, fma, stencil_args(*h, b), (hipStream_t)stream);
+}
+
+int vip_adaptive_run_c1(vip_adaptive_t h, const uint8_t* d_src, size_t src_pitch, uint8_t* d_dst, size_t dst_pitch,
+                        void* stream) {
+    if (!h) return VIP_ERR_INVALID_ARGUMENT;
+    return vip_adaptive_run_rows_c1(h, d_src, src_pitch, d_dst, dst_pitch, h->height, 0, 0, h->height, stream);
+}
+
 // ---------------------------------------------------------------- gradient
 int vip_gradient_u8(const uint8_t* d_src, float* d_dst, int width, int height, int src_ch, int numerics,
                     void* stream) {

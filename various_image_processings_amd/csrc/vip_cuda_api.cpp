@@ -141,6 +141,13 @@ void CudaAdaptiveBilateralFilter::Impl::execute(const std::uint8_t* const d_src,
                                                 void* stream) const {
     VIP_REPORT(vip_adaptive_run(handle_, d_src, (size_t)width_ * 3, d_dst, (size_t)width_ * 3, stream));
 }
+void CudaAdaptiveBilateralFilter::Impl::execute_c1(const std::uint8_t* const d_src, std::uint8_t* const d_dst) const {
+    execute_c1(d_src, d_dst, nullptr);
+}
+void CudaAdaptiveBilateralFilter::Impl::execute_c1(const std::uint8_t* const d_src, std::uint8_t* const d_dst,
+                                                   void* stream) const {
+    VIP_REPORT(vip_adaptive_run_c1(handle_, d_src, (size_t)width_, d_dst, (size_t)width_, stream));
+}
 
 CudaAdaptiveBilateralFilter::CudaAdaptiveBilateralFilter(const int width, const int height, const int ksize,
                                                          const float sigma_space, const float sigma_color)
@@ -155,6 +162,15 @@ void CudaAdaptiveBilateralFilter::execute(const std::uint8_t* const d_src, std::
 void CudaAdaptiveBilateralFilter::execute(const std::uint8_t* const d_src, std::uint8_t* const d_dst,
                                           void* stream) const {
     impl_->execute(d_src, d_dst, stream);
+}
+
+void CudaAdaptiveBilateralFilter::execute_c1(const std::uint8_t* const d_src, std::uint8_t* const d_dst) const {
+    impl_->execute_c1(d_src, d_dst);
+    VIP_REPORT(vip_device_synchronize());
+}
+void CudaAdaptiveBilateralFilter::execute_c1(const std::uint8_t* const d_src, std::uint8_t* const d_dst,
+                                             void* stream) const {
+    impl_->execute_c1(d_src, d_dst, stream);
 }
 
 // ------------------------------------------------------------ CudaBilateralTextureFilter

@@ -84,7 +84,7 @@ struct RtArgs {
 };
 
 // The launchers: vip_bilateral.hip (one translation unit per joint/fma pair), vip_adaptive.hip
-// (one per arithmetic), vip_stencil_rt.hip, vip_gray.hip, then vip_texture.hip. The stencil launchers
+// (one per arithmetic), vip_stencil_rt.hip, vip_gray.hip, vip_gray_adaptive.hip, then vip_texture.hip. The stencil launchers
 // return VIP_ERR_UNSUPPORTED_KSIZE for a radius they have no kernel for.
 int launch_bilateral_joint_fma(int radius, const StencilArgs& a, hipStream_t s);
 int launch_bilateral_joint_mul(int radius, const StencilArgs& a, hipStream_t s);
@@ -97,6 +97,9 @@ int launch_stencil_rt(const RtArgs& a, bool joint, bool adaptive, bool fma, hipS
 // own guide), 1 (gray guide) or 3 (interleaved 3-channel guide); radius 1..15 / runtime radius
 int launch_gray(int radius, int guide_channels, bool fma, const StencilArgs& a, hipStream_t s);
 int launch_gray_rt(const RtArgs& a, int guide_channels, bool fma, hipStream_t s);
+// vip_gray_adaptive.hip: the one-channel adaptive filter; radius 1..15 / runtime radius
+int launch_gray_adaptive(int radius, bool fma, const StencilArgs& a, hipStream_t s);
+int launch_gray_adaptive_rt(const RtArgs& a, bool fma, hipStream_t s);
 int launch_gradient_u8(const uint8_t* src, float* dst, int width, int height, int ch, hipStream_t stream);
 int launch_gradient_f32(const float* src, float* dst, int width, int height, int ch, bool fma, hipStream_t stream);
 int launch_blur_rtv(const uint8_t* img, const float* mag, float* blurred, float* rtv, int width, int height,

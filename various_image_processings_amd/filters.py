@@ -7,7 +7,8 @@ yuyuyu-bot/various_image_processings:
   with ``bilateral_filter(d_src, d_dst)`` and ``joint_bilateral_filter(d_src, d_guide, d_dst)``
   (include/cuda/bilateral_filter.hpp:9-24), and their one-channel forms ``bilateral_filter_c1(d_src,
   d_dst)`` / ``joint_bilateral_filter_c1(d_src, d_guide, guide_channels, d_dst)`` (no reference counterpart)
-* ``CudaAdaptiveBilateralFilter(...).execute(d_src, d_dst)`` (adaptive_bilateral_filter.hpp:9-19)
+* ``CudaAdaptiveBilateralFilter(...).execute(d_src, d_dst)`` (adaptive_bilateral_filter.hpp:9-19), and its
+  one-channel form ``execute_c1(d_src, d_dst)`` (no reference counterpart)
 * ``CudaBilateralTextureFilter(width, height, ksize=9, nitr=3).execute(d_src, d_dst)``
   (bilateral_texture_filter.hpp:9-12)
 * ``cuda_gradient(d_src, d_dst, width, height, src_ch=1)`` (gradient.hpp:13-23)
@@ -288,6 +289,18 @@ class _AdaptiveImpl(_Handle):
         call("vip_adaptive_run_rows", self._h, _ptr(d_src, p * int(row_hi)), p, _ptr(d_dst, p * int(out_rows)), p,
              int(out_rows), int(src_row0), int(row_lo), int(row_hi), _stream(stream))
 
+    # single-channel (8-bit gray) form, include/vip.h vip_adaptive_run_c1: d_src and d_dst are
+    # width * height bytes
+    def execute_c1(self, d_src, d_dst, stream=None):
+        p, n = self.width, self.width * self.height
+        call("vip_adaptive_run_c1", self._h, _ptr(d_src, n), p, _ptr(d_dst, n), p, _stream(stream))
+
+    def run_rows_c1(self, d_src, d_dst, out_rows, src_row0, row_lo, row_hi, stream=None):
+        """run_rows for one-channel images (include/vip.h vip_adaptive_run_rows_c1)."""
+        p = self.width
+        call("vip_adaptive_run_rows_c1", self._h, _ptr(d_src, p * int(row_hi)), p, _ptr(d_dst, p * int(out_rows)), p,
+             int(out_rows), int(src_row0), int(row_lo), int(row_hi), _stream(stream))
+
     def run_rows_batch(self, d_srcs, d_dsts, out_rows, src_row0, row_lo, row_hi, free_cus=0, stream=None):
         """include/vip.h vip_adaptive_run_rows_batch"""
         _run_batch("vip_adaptive_run_rows_batch", self._h, self.width * 3, d_srcs, d_dsts, out_rows, src_row0,
@@ -302,6 +315,11 @@ class CudaAdaptiveBilateralFilter:
 
     def execute(self, d_src, d_dst):
         self.impl_.execute(d_src, d_dst)
+        device_synchronize()
+
+    def execute_c1(self, d_src, d_dst):
+        """One-channel form (no reference counterpart; include/vip.h vip_adaptive_run_c1)."""
+        self.impl_.execute_c1(d_src, d_dst)
         device_synchronize()
 
 
