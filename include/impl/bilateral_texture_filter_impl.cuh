@@ -27,6 +27,9 @@ public:
 
     void execute(const std::uint8_t* const d_src, std::uint8_t* const d_dst);
     void execute(const std::uint8_t* const d_src, std::uint8_t* const d_dst, void* stream);
+    // one-channel form (vip_texture_run_c1)
+    void execute_c1(const std::uint8_t* const d_src, std::uint8_t* const d_dst);
+    void execute_c1(const std::uint8_t* const d_src, std::uint8_t* const d_dst, void* stream);
 
     // stage entry points (no synchronisation), raw device pointers
     void compute_blur_and_rtv(const std::uint8_t* d_image, const float* d_magnitude, float* d_blurred, float* d_rtv);
@@ -49,6 +52,7 @@ public:
 
 private:
     vip_texture_t handle_ = nullptr;
+    int width_ = 0;  // execute_c1's dense pitch
 };
 
 #endif  // VIP_IMPL_BILATERAL_TEXTURE_FILTER_IMPL_CUH

@@ -277,6 +277,39 @@ int vip_texture_run_timed(vip_texture_t h, const uint8_t* d_src, uint8_t* d_dst,
 #define VIP_TEXTURE_FUSED 1
 int vip_texture_set_mode(vip_texture_t h, int mode);
 
+/* ---- single-channel (8-bit gray) form (no reference counterpart). d_src and d_dst are one
+ * byte per pixel; the handle is the same vip_texture_t (ksize 1..24, even too). The result is,
+ * bit for bit, any channel of vip_texture_run on the frame (g, g, g): on a frame with three
+ * equal channels every stage produces three equal channels. It is NOT the (g, 0, 0) embedding
+ * of the gray bilateral and adaptive forms: the texture filter couples the channels in the
+ * intensity (b + g + r) / 3.f, in the gradient magnitude and in the guide's L1 distance, so
+ * (g, 0, 0) is a different image (its rtv is a third). One iteration on X, replicate border,
+ * R = ksize / 2, window K = 2R + 1 (divisions by ksize^2 even for even ksize):
+ *   mag       = sqrtf((float)(3 * (h*h + v*v))),  h = X(x+1,y) - X(x-1,y), v likewise (the exact
+ *               integer sum over three equal channels, not sqrt(3) times a one-channel magnitude)
+ *   intensity = (3 g) / 3.f == (float)g, so imax / imin are the integer max / min of g over the
+ *               window (initial values 0 and 256)
+ *   blurred   = (float)(sum of g over the window) / (ksize * ksize)
+ *   rtv       = (imax - imin) * max(mag) / (sum(mag) + 1e-9), the sum in row-major order; the
+ *               divide in double in the CUDA profile, in float with 1e-9f in the CPP profile
+ *   G         = u8(alpha * blurred(min) + (1 - alpha) * blurred(c) + 0.5f) clamped to 0..255
+ *               (fused in the CUDA profile), min the first strict argmin of rtv over the window,
+ *               alpha = 2 / (1 + exp(sigma_alpha * (rtv(c) - rtv(min)))) - 1, sigma_alpha = 1 / (5 ksize)
+ *   X'        = the joint bilateral of X under the gray guide G, ksize 2k - 1, sigma_space k - 1:
+ *               w = ws[ky,kx] * wc[3 * |G_n - G_c|] with wc the 768-entry LUT of sigma_color
+ *               sqrt(3) (3 * 255 = 765 lies inside it), sums as vip_joint_bilateral_run_c1
+ * Iteration i reads X_i and writes X_{i+1}; the intermediates and the guide live in the
+ * handle's scratch frames (no allocation per call; vip_texture_scratch_bytes is unchanged).
+ * Two launches per iteration (vip::gray_texture_guide_kernel, then vip::gray_kernel with a gray
+ * guide for k <= 16 or vip::gray_rt_kernel above and under VIP_PATH_RUNTIME);
+ * vip_texture_set_mode is ignored. nitr 0 copies width bytes per row. d_dst == d_src with
+ * equal pitches is allowed (through a scratch copy). Any base address and pitch work for d_src
+ * and d_dst; no byte of d_dst at column >= width is written. VIP_ERR_INVALID_ARGUMENT: null
+ * handle or pointer, a pitch < width. There is no row-slab, sharded or one-launch form, and no
+ * one-channel vip_texture_blur_rtv / vip_texture_guide. */
+int vip_texture_run_c1(vip_texture_t h, const uint8_t* d_src, size_t src_pitch, uint8_t* d_dst, size_t dst_pitch,
+                       void* stream);
+
 /* Row-slab form of one texture iteration for a row-sharded frame (SURVEY §8(f)3;
  * the reference is single-GPU). d_src is a dense slab of the handle's width x
  * height (pitch width*3) whose rows [row_lo, row_hi) are valid frame rows: every

@@ -22,6 +22,9 @@
 //                                       is a gray file, OUT is written with one channel)
 //   vip_filter texture   IN OUT [ksize=9] [nitr=3]
 //                                       (sample/bilateral_texture_filter/main.cpp:15-17)
+//   vip_filter texture-gray IN OUT [ksize=9] [nitr=3]
+//                                       (one-channel CudaBilateralTextureFilter::execute_c1; IN
+//                                       is a gray file, OUT is written with one channel)
 //   vip_filter gradient  IN OUT         (sample/gradient/main.cpp:23-40; OUT is the
 //                                       magnitude scaled to 0..255 by its maximum as the
 //                                       sample's convert_to_u8 displays it, or the raw
@@ -57,6 +60,7 @@ static int usage() {
                  "        vip_filter adaptive IN OUT [ksize] [sigma_space] [sigma_color]\n"
                  "        vip_filter adaptive-gray IN OUT [ksize] [sigma_space] [sigma_color]\n"
                  "        vip_filter texture IN OUT [ksize] [nitr]\n"
+                 "        vip_filter texture-gray IN OUT [ksize] [nitr]\n"
                  "        vip_filter gradient IN OUT\n"
                  "        vip_filter convert IN OUT\n"
                  "        options: --repeat N\n");
@@ -94,7 +98,7 @@ int main(int argc, char** argv) {
     }
     if (args.size() < 3) return usage();
     const std::string mode = args[0];
-    const bool gray = mode == "gray" || mode == "joint-gray" || mode == "adaptive-gray";
+    const bool gray = mode == "gray" || mode == "joint-gray" || mode == "adaptive-gray" || mode == "texture-gray";
     const bool joint = mode == "joint" || mode == "joint-gray";
     const size_t np = joint ? 4 : 3;  // index of the first numeric parameter
     if (args.size() < np) return usage();
@@ -135,7 +139,10 @@ int main(int argc, char** argv) {
             d_src.upload(in.data.data());
             const int ksize = int_arg(np, 9);
             const float sigma_space = flt_arg(np + 1, 10.f), sigma_color = flt_arg(np + 2, 30.f);
-            if (mode == "adaptive-gray") {
+            if (mode == "texture-gray") {
+                CudaBilateralTextureFilter filter(W, H, ksize, int_arg(np + 1, 3));
+                run_timed("bilateral texture filter (gray)", repeat, [&] { filter.execute_c1(d_src.get(), d_dst.get()); });
+            } else if (mode == "adaptive-gray") {
                 CudaAdaptiveBilateralFilter filter(W, H, ksize, sigma_space, sigma_color);
                 run_timed("adaptive bilateral filter (gray)", repeat, [&] { filter.execute_c1(d_src.get(), d_dst.get()); });
             } else {

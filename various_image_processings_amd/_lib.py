@@ -93,6 +93,7 @@ SIGNATURES = {
     "vip_texture_destroy": (_c_int, [_c_void_p]),
     "vip_texture_run": (_c_int, [_c_void_p, _c_void_p, _c_void_p, _c_void_p]),
     "vip_texture_run_timed": (_c_int, [_c_void_p, _c_void_p, _c_void_p, _c_void_p, ctypes.POINTER(_c_void_p)]),
+    "vip_texture_run_c1": (_c_int, [_c_void_p, _c_void_p, _c_size_t, _c_void_p, _c_size_t, _c_void_p]),
     "vip_texture_halo_rows": (_c_int, [_c_int]),
     "vip_texture_set_mode": (_c_int, [_c_void_p, _c_int]),
     "vip_bilateral_set_waves": (_c_int, [_c_int]),

@@ -344,6 +344,10 @@ struct vip_texture_s {
     vip_bilateral_t jbf;
     uint8_t* d_ping[2];
     uint8_t* d_guide;
+    // vip_texture_run_c1: the gray guide's colour table, entry d = entry 3d of the JBF's LUT
+    // (three equal channels: L1 distance 3 |G_n - G_c|), and its leading nonzero entries
+    float* d_color_c1;
+    int lut_nonzero_c1;
 };
 
 namespace {
@@ -768,7 +772,20 @@ int vip_texture_destroy(vip_texture_t h) {
     (void)hipFree(h->d_ping[0]);
     (void)hipFree(h->d_ping[1]);
     (void)hipFree(h->d_guide);
+    (void)hipFree(h->d_color_c1);
     delete h;
+    return 0;
+}
+
+static int upload_color_c1(vip_texture_t h) {
+    float wc[768], c1[256];
+    build_color(768, 1.73205080757f, h->numerics, wc);
+    for (int d = 0; d < 256; ++d) c1[d] = wc[3 * d];
+    int nz = 256;
+    while (nz > 0 && c1[nz - 1] == 0.f) --nz;
+    h->lut_nonzero_c1 = nz;
+    VIP_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&h->d_color_c1), sizeof(c1)));
+    VIP_HIP_CHECK(hipMemcpy(h->d_color_c1, c1, sizeof(c1), hipMemcpyHostToDevice));
     return 0;
 }
 
@@ -790,6 +807,7 @@ int vip_texture_create(vip_texture_t* out, int width, int height, int ksize, int
     if (!rc) rc = (int)hipMalloc(reinterpret_cast<void**>(&h->d_ping[0]), frame);
     if (!rc) rc = (int)hipMalloc(reinterpret_cast<void**>(&h->d_ping[1]), frame);
     if (!rc) rc = (int)hipMalloc(reinterpret_cast<void**>(&h->d_guide), frame);
+    if (!rc) rc = upload_color_c1(h);
     if (rc) {
         vip_texture_destroy(h);
         return rc;
@@ -872,6 +890,53 @@ int vip_texture_run(vip_texture_t h, const uint8_t* d_src, uint8_t* d_dst, void*
 int vip_texture_run_timed(vip_texture_t h, const uint8_t* d_src, uint8_t* d_dst, void* stream, void* const* events) {
     if (!events) return VIP_ERR_INVALID_ARGUMENT;
     return texture_run(h, d_src, d_dst, stream, events);
+}
+
+// The one-channel filter (vip.h): per iteration the one-channel guide stage
+// (vip_gray_texture.hip) and the gray joint bilateral under that gray guide (vip_gray.hip),
+// with the handle's 256-entry table. Gray frames in the handle's u8x3 scratch frames: rows
+// of gray_pitch bytes (dword-aligned rows from width 4 on; never more than a third of a frame).
+static size_t gray_pitch(int width) { return width < 4 ? (size_t)width : (size_t)round_up(width, 4); }
+
+int vip_texture_run_c1(vip_texture_t h, const uint8_t* d_src, size_t src_pitch, uint8_t* d_dst, size_t dst_pitch,
+                       void* stream) {
+    if (!h || !d_src || !d_dst || src_pitch < (size_t)h->width || dst_pitch < (size_t)h->width)
+        return VIP_ERR_INVALID_ARGUMENT;
+    const hipStream_t s = (hipStream_t)stream;
+    const size_t gp = gray_pitch(h->width);
+    if (h->nitr == 0) {
+        if (d_src != d_dst)
+            VIP_HIP_CHECK(hipMemcpy2DAsync(d_dst, dst_pitch, d_src, src_pitch, (size_t)h->width, (size_t)h->height,
+                                           hipMemcpyDeviceToDevice, s));
+        return 0;
+    }
+    const uint8_t* cur = d_src;
+    size_t cur_pitch = src_pitch;
+    if (d_src == d_dst) {  // the last JBF must not write the frame it reads
+        VIP_HIP_CHECK(hipMemcpy2DAsync(h->d_ping[1], gp, d_src, src_pitch, (size_t)h->width, (size_t)h->height,
+                                       hipMemcpyDeviceToDevice, s));
+        cur = h->d_ping[1];
+        cur_pitch = gp;
+    }
+    StencilHandle jbf = *h->jbf;  // the JBF's geometry and spatial tables, the gray guide's colour table
+    jbf.d_color = h->d_color_c1;
+    jbf.lut_nonzero = h->lut_nonzero_c1;
+    const bool fma = h->numerics == VIP_NUMERICS_CUDA;
+    for (int it = 0; it < h->nitr; ++it) {
+        const bool last = it == h->nitr - 1;
+        uint8_t* next = last ? d_dst : (cur == h->d_ping[0] ? h->d_ping[1] : h->d_ping[0]);
+        const size_t next_pitch = last ? dst_pitch : gp;
+        int rc = launch_gray_texture_guide_rows(cur, cur_pitch, h->d_guide, gp, h->width, 0, h->height, 0, h->height,
+                                                h->ksize, !fma, s);
+        if (rc) return rc;
+        const RowBand b{cur, cur_pitch, h->d_guide, gp, next, next_pitch, h->height, 0, 0, h->height};
+        rc = use_runtime_kernel(jbf.radius) ? launch_gray_rt(rt_args(jbf, b), 1, fma, s)
+                                            : launch_gray(jbf.radius, 1, fma, stencil_args(jbf, b), s);
+        if (rc) return rc;
+        cur = next;
+        cur_pitch = next_pitch;
+    }
+    return 0;
 }
 
 int vip_texture_halo_rows(int ksize) {

@@ -174,7 +174,8 @@ void CudaAdaptiveBilateralFilter::execute_c1(const std::uint8_t* const d_src, st
 }
 
 // ------------------------------------------------------------ CudaBilateralTextureFilter
-CudaBilateralTextureFilter::Impl::Impl(const int width, const int height, const int ksize, const int nitr) {
+CudaBilateralTextureFilter::Impl::Impl(const int width, const int height, const int ksize, const int nitr)
+    : width_(width) {
     const int rc = vip_texture_create(&handle_, width, height, ksize, nitr, VIP_NUMERICS_CUDA);
     if (rc) fail("CudaBilateralTextureFilter", rc);
 }
@@ -186,6 +187,13 @@ void CudaBilateralTextureFilter::Impl::execute(const std::uint8_t* const d_src, 
 void CudaBilateralTextureFilter::Impl::execute(const std::uint8_t* const d_src, std::uint8_t* const d_dst,
                                                void* stream) {
     VIP_REPORT(vip_texture_run(handle_, d_src, d_dst, stream));
+}
+void CudaBilateralTextureFilter::Impl::execute_c1(const std::uint8_t* const d_src, std::uint8_t* const d_dst) {
+    execute_c1(d_src, d_dst, nullptr);
+}
+void CudaBilateralTextureFilter::Impl::execute_c1(const std::uint8_t* const d_src, std::uint8_t* const d_dst,
+                                                  void* stream) {
+    VIP_REPORT(vip_texture_run_c1(handle_, d_src, (size_t)width_, d_dst, (size_t)width_, stream));
 }
 
 void CudaBilateralTextureFilter::Impl::compute_blur_and_rtv(const std::uint8_t* d_image, const float* d_magnitude,
@@ -210,6 +218,15 @@ void CudaBilateralTextureFilter::execute(const std::uint8_t* const d_src, std::u
 
 void CudaBilateralTextureFilter::execute(const std::uint8_t* const d_src, std::uint8_t* const d_dst, void* stream) {
     impl_->execute(d_src, d_dst, stream);
+}
+
+void CudaBilateralTextureFilter::execute_c1(const std::uint8_t* const d_src, std::uint8_t* const d_dst) {
+    impl_->execute_c1(d_src, d_dst);
+    VIP_REPORT(vip_device_synchronize());
+}
+void CudaBilateralTextureFilter::execute_c1(const std::uint8_t* const d_src, std::uint8_t* const d_dst,
+                                            void* stream) {
+    impl_->execute_c1(d_src, d_dst, stream);
 }
 
 // ------------------------------------------------------------ cuda_gradient

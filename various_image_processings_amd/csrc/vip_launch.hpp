@@ -84,7 +84,7 @@ struct RtArgs {
 };
 
 // The launchers: vip_bilateral.hip (one translation unit per joint/fma pair), vip_adaptive.hip
-// (one per arithmetic), vip_stencil_rt.hip, vip_gray.hip, vip_gray_adaptive.hip, then vip_texture.hip. The stencil launchers
+// (one per arithmetic), vip_stencil_rt.hip, vip_gray.hip, vip_gray_adaptive.hip, then vip_texture.hip and vip_gray_texture.hip. The stencil launchers
 // return VIP_ERR_UNSUPPORTED_KSIZE for a radius they have no kernel for.
 int launch_bilateral_joint_fma(int radius, const StencilArgs& a, hipStream_t s);
 int launch_bilateral_joint_mul(int radius, const StencilArgs& a, hipStream_t s);
@@ -111,6 +111,10 @@ int launch_texture_guide_fused(const uint8_t* img, uint8_t* guide, int width, in
 int launch_texture_guide_fused_rows(const uint8_t* img, uint8_t* guide, int width, int lo, int hi, int gy0, int gy1,
                                     int ksize, bool cpp, hipStream_t stream);
 int launch_texture_iteration_fused(const StencilArgs& a, int ksize, bool cpp, hipStream_t stream);
+// vip_gray_texture.hip: the fused guide stage on a one-channel frame (img: any base and pitch);
+// rows [lo, hi) are valid, guide rows [gy0, gy1) inside them are produced
+int launch_gray_texture_guide_rows(const uint8_t* img, size_t img_pitch, uint8_t* guide, size_t guide_pitch, int width,
+                                   int lo, int hi, int gy0, int gy1, int ksize, bool cpp, hipStream_t stream);
 
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per kernel and device (the
 // attribute is per device and one process may drive several). `devs` is the kernel's

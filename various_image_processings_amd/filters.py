@@ -10,7 +10,8 @@ yuyuyu-bot/various_image_processings:
 * ``CudaAdaptiveBilateralFilter(...).execute(d_src, d_dst)`` (adaptive_bilateral_filter.hpp:9-19), and its
   one-channel form ``execute_c1(d_src, d_dst)`` (no reference counterpart)
 * ``CudaBilateralTextureFilter(width, height, ksize=9, nitr=3).execute(d_src, d_dst)``
-  (bilateral_texture_filter.hpp:9-12)
+  (bilateral_texture_filter.hpp:9-12), and its one-channel form ``execute_c1(d_src, d_dst)`` (no reference
+  counterpart)
 * ``cuda_gradient(d_src, d_dst, width, height, src_ch=1)`` (gradient.hpp:13-23)
 * ``DeviceImage(width, height, channels=1, dtype)`` with upload/download/get (device_image.hpp:4-16)
 
@@ -344,6 +345,12 @@ class _TextureImpl(_Handle):
         n = self.width * self.height * 3
         call("vip_texture_run", self._h, _ptr(d_src, n), _ptr(d_dst, n), _stream(stream))
 
+    # single-channel (8-bit gray) form, include/vip.h vip_texture_run_c1: d_src and d_dst are
+    # width * height bytes; any channel of execute() on the frame (g, g, g)
+    def execute_c1(self, d_src, d_dst, stream=None):
+        p, n = self.width, self.width * self.height
+        call("vip_texture_run_c1", self._h, _ptr(d_src, n), p, _ptr(d_dst, n), p, _stream(stream))
+
     def execute_timed(self, d_src, d_dst, events, stream=None):
         """execute() with per-stage timestamps (include/vip.h vip_texture_run_timed):
         `events` = 2 * nitr + 1 torch.cuda.Event(enable_timing=True), recorded before
@@ -383,6 +390,11 @@ class CudaBilateralTextureFilter:
 
     def execute(self, d_src, d_dst):
         self.impl_.execute(d_src, d_dst)
+        device_synchronize()
+
+    def execute_c1(self, d_src, d_dst):
+        """One-channel form (no reference counterpart; include/vip.h vip_texture_run_c1)."""
+        self.impl_.execute_c1(d_src, d_dst)
         device_synchronize()
 
 
