@@ -11,6 +11,8 @@ mkdir -p ../../variants /tmp/ovar_$name
 hipcc --offload-arch=gfx950 -O3 -std=c++20 -fPIC -ffp-contract=off -fno-slp-vectorize -I../../include -I. "$@" \
   -c $src -o /tmp/ovar_$name/v.o
 O=../../build/cmake/CMakeFiles
-others=$(ls $O/vip_{bil,ada,texture,capi,stencil_rt}*.dir/various_image_processings_amd/csrc/*.o | grep -v "/$target.dir/")
+# every other object of libvip_hip.so (vip_hip.dir holds the C++ API; vip_shard is a library of its own):
+# assumes every other vip_*.dir target with a source in csrc/ is an object library of libvip_hip.so
+others=$(ls $O/vip_*.dir/various_image_processings_amd/csrc/*.o | grep -v -e "/$target\.dir/" -e '/vip_shard\.dir/')
 hipcc --offload-arch=gfx950 -shared -o ../../variants/$name.so /tmp/ovar_$name/v.o $others
 echo built variants/$name.so

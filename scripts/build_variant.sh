@@ -13,8 +13,9 @@ hipcc $F -DVIP_ONLY_R7 -c vip_bilateral.hip -o /tmp/var_$name/bm.o
 hipcc $F -DVIP_ONLY_R7 -DVIP_BIL_JOINT -c vip_bilateral.hip -o /tmp/var_$name/bjm.o
 hipcc $F -DVIP_ONLY_R7 -DVIP_ADA_FMA -c vip_adaptive.hip -o /tmp/var_$name/a.o
 hipcc $F -DVIP_ONLY_R7 -c vip_adaptive.hip -o /tmp/var_$name/am.o
-# the texture, C ABI and C++ API objects of the in-place CMake build (__graft_entry__.build())
+# every other object of libvip_hip.so from the in-place CMake build (__graft_entry__.build())
 O=../../build/cmake/CMakeFiles
-hipcc --offload-arch=gfx950 -shared -o ../../variants/$name.so /tmp/var_$name/*.o \
-  $(ls $O/vip_{texture,capi,stencil_rt,gray}.dir/various_image_processings_amd/csrc/*.o $O/vip_hip.dir/various_image_processings_amd/csrc/*.o)
+# (assumes every vip_*.dir target with a source in csrc/ but vip_shard is an object library of libvip_hip.so)
+others=$(ls $O/vip_*.dir/various_image_processings_amd/csrc/*.o | grep -v -e '/vip_bil_[^/]*\.dir/' -e '/vip_ada_[^/]*\.dir/' -e '/vip_shard\.dir/')
+hipcc --offload-arch=gfx950 -shared -o ../../variants/$name.so /tmp/var_$name/*.o $others
 echo built variants/$name.so

@@ -9,7 +9,9 @@ recorder (include/vip.h vip_kernel_timing_*); the median of each. Three passes p
 table gives the median of the three pass medians, every pass median, and the spread (max - min)
 of the 3-channel pass medians. Accepted when, at every ksize, the gray median is below the
 3-channel median by more than that spread. Prints the table, and with --out FILE writes it
-there (profiles/gray_adaptive_4k_ab.txt). Exit status 1 when the acceptance line is missed."""
+there (profiles/gray_adaptive_4k_ab.txt). Exit status 1 when the acceptance line is missed.
+--numerics 1 times the C++ profile's kernels; --lib FILE loads an alternative library build
+(scripts/build_*variant.sh)."""
 import argparse
 import statistics
 import sys
@@ -17,17 +19,22 @@ import time
 
 import torch
 
-sys.path.insert(0, ".")
-import various_image_processings_amd as vip  # noqa: E402,F401
-from various_image_processings_amd.filters import _AdaptiveImpl, kernel_timing  # noqa: E402
-
 ap = argparse.ArgumentParser()
 ap.add_argument("--out", default=None)
+ap.add_argument("--lib", default=None)
+ap.add_argument("--numerics", type=int, default=0)
 ap.add_argument("--launches", type=int, default=60)
 ap.add_argument("--passes", type=int, default=3)
 ap.add_argument("--settle", type=float, default=2.0)
 ap.add_argument("--ksizes", type=int, nargs="+", default=[5, 15, 31])
 opt = ap.parse_args()
+
+sys.path.insert(0, ".")
+if opt.lib:
+    import various_image_processings_amd._lib as L
+    L.LIB_PATH = opt.lib
+import various_image_processings_amd as vip  # noqa: E402,F401
+from various_image_processings_amd.filters import _AdaptiveImpl, kernel_timing  # noqa: E402
 
 W, H = 3840, 2160
 torch.cuda.set_device(0)
@@ -61,13 +68,13 @@ def fmt(v):
 
 
 ok = True
-lines = [f"# gray vs 3-channel adaptive bilateral, {W} x {H} uniform random, CUDA numerics; per pass the median kernel "
+lines = [f"# gray vs 3-channel adaptive bilateral, {W} x {H} uniform random, numerics {opt.numerics}; per pass the median kernel "
          f"duration of {opt.launches} launches each, interleaved on one stream; {opt.passes} passes "
          f"({torch.cuda.get_device_name(0)})",
          f"{'ksize':>5}{'gray us':>10}{'3ch us':>10}{'gray/3ch':>10}{'3ch spread':>12}  accepted  "
          f"gray passes | 3ch passes | kernels"]
 for k in opt.ksizes:
-    impl = _AdaptiveImpl(W, H, k)
+    impl = _AdaptiveImpl(W, H, k, numerics=opt.numerics)
     ug, u3, names = [], [], None
     for _ in range(opt.passes):
         (ng, a), (n3, b) = one_pass(lambda: impl.execute_c1(g, d1), lambda: impl.execute(rgb, d3))

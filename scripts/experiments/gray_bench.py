@@ -4,9 +4,11 @@ before it existed (widen, filter, take one channel back -- only the filter is ti
 3840 x 2160 uniform-random frame, CUDA numerics, ksize 5, 15 and 31: after a 2 s settle, 60
 launches of the gray filter and 60 of the 3-channel filter of the same width, height and
 ksize, interleaved on one stream; each kernel's own duration from the kernel-timing
-recorder (include/vip.h vip_kernel_timing_*); the median of each. Prints a table, and
+recorder (include/vip.h vip_kernel_timing_*); the median of each. --passes N repeats that N
+times and gives the median of the pass medians and every pass median. Prints a table, and
 with --out FILE writes it there (profiles/gray_4k_ab.txt). --forms adds the gray-guide and
-RGB-guide joint forms against the 3-channel joint filter."""
+RGB-guide joint forms against the 3-channel joint filter; --numerics 1 times the C++ profile's
+kernels; --lib FILE loads an alternative library build (scripts/build_*variant.sh)."""
 import argparse
 import statistics
 import sys
@@ -14,17 +16,23 @@ import time
 
 import torch
 
-sys.path.insert(0, ".")
-import various_image_processings_amd as vip  # noqa: E402
-from various_image_processings_amd.filters import _BilateralImpl, kernel_timing  # noqa: E402
-
 ap = argparse.ArgumentParser()
 ap.add_argument("--out", default=None)
+ap.add_argument("--lib", default=None)
+ap.add_argument("--numerics", type=int, default=0)
 ap.add_argument("--launches", type=int, default=60)
+ap.add_argument("--passes", type=int, default=1)
 ap.add_argument("--settle", type=float, default=2.0)
 ap.add_argument("--ksizes", type=int, nargs="+", default=[5, 15, 31])
 ap.add_argument("--forms", action="store_true")
 opt = ap.parse_args()
+
+sys.path.insert(0, ".")
+if opt.lib:
+    import various_image_processings_amd._lib as L
+    L.LIB_PATH = opt.lib
+import various_image_processings_amd as vip  # noqa: E402,F401
+from various_image_processings_amd.filters import _BilateralImpl, kernel_timing  # noqa: E402
 
 W, H = 3840, 2160
 torch.cuda.set_device(0)
@@ -55,11 +63,16 @@ def ab(impl, gray_call, rgb_call):
     return (a[0][0], statistics.median(ms for _, ms in a) * 1e3), (b[0][0], statistics.median(ms for _, ms in b) * 1e3)
 
 
-lines = [f"# gray vs 3-channel bilateral, {W} x {H} uniform random, CUDA numerics; median kernel duration of "
-         f"{opt.launches} launches each, interleaved on one stream ({torch.cuda.get_device_name(0)})",
-         f"{'form':<12}{'ksize':>6}{'gray us':>10}{'3ch us':>10}{'gray/3ch':>10}  kernels"]
+def fmt(v):
+    return "/".join(f"{x:.2f}" for x in v)
+
+
+lines = [f"# gray vs 3-channel bilateral, {W} x {H} uniform random, numerics {opt.numerics}; per pass the median kernel "
+         f"duration of {opt.launches} launches each, interleaved on one stream; {opt.passes} passes "
+         f"({torch.cuda.get_device_name(0)})",
+         f"{'form':<12}{'ksize':>6}{'gray us':>10}{'3ch us':>10}{'gray/3ch':>10}  gray passes | 3ch passes | kernels"]
 for k in opt.ksizes:
-    impl = _BilateralImpl(W, H, k)
+    impl = _BilateralImpl(W, H, k, numerics=opt.numerics)
     cases = [("plain", lambda: impl.bilateral_filter_c1(g, d1), lambda: impl.bilateral_filter(rgb, d3))]
     if opt.forms and k <= 47:
         cases.append(("gray-guide", lambda: impl.joint_bilateral_filter_c1(g, gg, 1, d1),
@@ -67,8 +80,13 @@ for k in opt.ksizes:
         cases.append(("rgb-guide", lambda: impl.joint_bilateral_filter_c1(g, rgb2, 3, d1),
                       lambda: impl.joint_bilateral_filter(rgb, rgb2, d3)))
     for form, fg, f3 in cases:
-        (ng, ug), (n3, u3) = ab(impl, fg, f3)
-        lines.append(f"{form:<12}{k:>6}{ug:>10.2f}{u3:>10.2f}{ug / u3:>10.3f}  {ng} | {n3}")
+        pg, p3 = [], []
+        for _ in range(opt.passes):
+            (ng, ug), (n3, u3) = ab(impl, fg, f3)
+            pg.append(ug)
+            p3.append(u3)
+        ug, u3 = statistics.median(pg), statistics.median(p3)
+        lines.append(f"{form:<12}{k:>6}{ug:>10.2f}{u3:>10.2f}{ug / u3:>10.3f}  {fmt(pg)} | {fmt(p3)} | {ng} | {n3}")
         print(lines[-1], flush=True)
 text = "\n".join(lines) + "\n"
 print(text)

@@ -26,64 +26,14 @@
 //       RowStream), the next tile's HBM reads in flight under the current tile's taps.
 //   gray_rt_kernel<GUIDE, FMA>     radius a kernel argument (0 and 16..32, or every radius
 //       under VIP_PATH_RUNTIME); one workgroup per 64 x 64 tile, 4 outputs per thread, taps
-//       in blocks of 4 with exact zero weights outside the disc (as vip_stencil_rt.hip).
+//       in blocks of 4 with exact zero weights outside the disc (as vip_stencil_rt.hip;
+//       tile geometry and launch: vip_rt.hpp).
+// The tap loop of a tile row, gray_row_taps, is vip_gray.hpp's, here with the GraySad index.
 // Both numerics profiles (FMA: explicit __builtin_fmaf; otherwise mul + add, the build
 // has -ffp-contract=off) are instantiated here.
 #include "vip_gray.hpp"
 
 namespace vip {
-
-// The tap loop of one tile row (row_taps' one-accumulator form): neighbour column j serves
-// output i at kx = j - L - i; per output the taps run in ascending kx.
-template <int HW, int L, int C0, int NC, bool FMA, int P, int GUIDE>
-__device__ __forceinline__ void gray_row_taps(const uint32_t* plane, int row_off, const float (&wsv)[HW + 1],
-                                              const char* lut, uint32_t lane4, const uint32_t (&ctr)[P],
-                                              float (&s)[P], float (&sk)[P]) {
-    using W = GrayWord<GUIDE>;
-    constexpr int D = kPipeDepth, NB = D + 1;
-    constexpr int J0 = L - HW, J1 = L + P - 1 + HW;
-    constexpr int LA = D + kRowLookahead;
-    static_assert(J0 >= 4 * C0 && J1 < 4 * (C0 + NC), "row chunk range");
-    auto chunk = [](int j) constexpr { return (j - 4 * C0) >> 2; };
-    constexpr int PRE = chunk(J0 + LA < J1 ? J0 + LA : J1);
-    RowStream<C0, NC, false> row(plane, plane, row_off);
-#pragma unroll
-    for (int q = 0; q <= PRE; ++q) row.load(q);
-    float wc[NB][P], nf[NB];
-    auto issue = [&](int j) {
-        const uint32_t w = row.guide(j - 4 * C0);
-        const uint32_t g = W::guide(w);
-        const int b = (j - J0) % NB;
-        nf[b] = W::source(w);
-#pragma unroll
-        for (int i = 0; i < P; ++i) {
-            const int kx = j - L - i;
-            if (kx < -HW || kx > HW) continue;
-            const uint32_t d = __builtin_amdgcn_sad_u8(g, ctr[i], 0u);
-            wc[b][i] = *reinterpret_cast<const float*>(lut + ((d << 7) | lane4));
-        }
-    };
-#pragma unroll
-    for (int j = J0; j < J0 + D && j <= J1; ++j) issue(j);
-#pragma unroll
-    for (int j = J0; j <= J1; ++j) {
-        if (j + LA <= J1 && ((j + LA) & 3) == 0 && chunk(j + LA) > PRE) row.load(chunk(j + LA));
-        if (j + D <= J1) issue(j + D);
-        const int b = (j - J0) % NB;
-#pragma unroll
-        for (int i = 0; i < P; ++i) {
-            const int kx = j - L - i;
-            if (kx < -HW || kx > HW) continue;
-            const float w = wc[b][i] * wsv[kx < 0 ? -kx : kx];
-            if constexpr (FMA)
-                s[i] = __builtin_fmaf(nf[b], w, s[i]);
-            else
-                s[i] = s[i] + nf[b] * w;
-            sk[i] = sk[i] + w;
-        }
-        __builtin_amdgcn_sched_barrier(0);
-    }
-}
 
 constexpr int kGrayP = 8, kGrayWaves = 16;
 template <int R, int GUIDE>
@@ -133,16 +83,16 @@ __global__ __launch_bounds__(kGrayWaves * 64) void gray_kernel(const StencilArgs
             pf.issue(a, (n % a.tiles_x) * G::TW, (n / a.tiles_x) * TH);
         }
         if (ty0 + wave * G::RPW < a.out_rows) {  // wave-uniform: skip rows past the band
-            uint32_t ctr[P];
+            GraySad<GUIDE, P> dist;
             {
                 const uint4* c = reinterpret_cast<const uint4*>(plane + (ty + R) * G::S + tx * P + G::L);
 #pragma unroll
                 for (int q = 0; q < P / 4; ++q) {
                     const uint4 v = c[q];
-                    ctr[4 * q + 0] = W::guide(v.x);
-                    ctr[4 * q + 1] = W::guide(v.y);
-                    ctr[4 * q + 2] = W::guide(v.z);
-                    ctr[4 * q + 3] = W::guide(v.w);
+                    dist.ctr[4 * q + 0] = W::guide(v.x);
+                    dist.ctr[4 * q + 1] = W::guide(v.y);
+                    dist.ctr[4 * q + 2] = W::guide(v.z);
+                    dist.ctr[4 * q + 3] = W::guide(v.w);
                 }
             }
             float s[P], sk[P];
@@ -160,7 +110,7 @@ __global__ __launch_bounds__(kGrayWaves * 64) void gray_kernel(const StencilArgs
                 float wsv[HW + 1];
 #pragma unroll
                 for (int k = 0; k <= HW; ++k) wsv[k] = ws[k];
-                gray_row_taps<HW, G::L, C0, NC, FMA, P, GUIDE>(plane, row_off, wsv, lut_bytes, lane4, ctr, s, sk);
+                gray_row_taps<HW, G::L, C0, NC, FMA, P>(plane, row_off, wsv, lut_bytes, lane4, dist, s, sk);
                 // pin the accumulators at the row's end (fence_accumulators)
 #pragma unroll
                 for (int i = 0; i < P; ++i) __asm__ volatile("" : "+v"(s[i]), "+v"(sk[i]));
@@ -227,13 +177,13 @@ struct GrayRtWin {
 };
 
 template <int GUIDE, bool FMA>
-__global__ __launch_bounds__(kGrayRtWaves * 64) void gray_rt_kernel(const RtArgs a) {
+__global__ __launch_bounds__(kRtWaves * 64) void gray_rt_kernel(const RtArgs a) {
     using W = GrayWord<GUIDE>;
-    constexpr int P = kGrayRtP, NT = kGrayRtWaves * 64, TH = kGrayRtWaves * 4;
+    constexpr int P = kRtP, NT = kRtWaves * 64, TH = kRtWaves * 4;
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     const int R = a.R, L = a.L, S = a.S;
     const int rows = TH + 2 * R;
-    const int pw = gray_rt_plane_words(R, L, S);
+    const int pw = rt_plane_words(R, L, S);
     uint32_t* const plane = lds;
     uint32_t* const lut = lds + pw;
 
@@ -243,7 +193,7 @@ __global__ __launch_bounds__(kGrayRtWaves * 64) void gray_rt_kernel(const RtArgs
     const int tx = lane & 15;
     const int ty = wave * 4 + (lane >> 4);
     const int tile = blockIdx.x;
-    const int tx0 = (tile % a.tiles_x) * kGrayRtTW, ty0 = (tile / a.tiles_x) * TH;
+    const int tx0 = (tile % a.tiles_x) * kRtTW, ty0 = (tile / a.tiles_x) * TH;
 
     // colour LUT: word d * 32 + c = color[d]
     for (int q = tid; q < W::ENTRIES * kGrayCopies / 4; q += NT) {
@@ -254,7 +204,7 @@ __global__ __launch_bounds__(kGrayRtWaves * 64) void gray_rt_kernel(const RtArgs
     // reads up to 4 words past its apron (weight 0), and a zero word's distance to any
     // centre stays inside the LUT (d <= 255, or 765 with a 3-channel guide)
     {
-        const int gpr = S / 4, valid = (kGrayRtTW + 2 * L) / 4;
+        const int gpr = S / 4, valid = (kRtTW + 2 * L) / 4;
         for (int q = tid; q < rows * gpr; q += NT) {
             const int r = q / gpr, gc = q - r * gpr;
             uint4 w = make_uint4(0u, 0u, 0u, 0u);
@@ -342,21 +292,9 @@ __global__ __launch_bounds__(kGrayRtWaves * 64) void gray_rt_kernel(const RtArgs
 
 template <int GUIDE, bool FMA>
 static int launch_gray_rt_g(RtArgs a, hipStream_t stream) {
-    if (a.R < 0 || a.R > kRtMaxRadius) return VIP_ERR_UNSUPPORTED_KSIZE;
-    a.L = round_up(a.R, 4);
-    a.S = gray_rt_stride(a.L);
-    a.tiles_x = (a.width + kGrayRtTW - 1) / kGrayRtTW;
-    const long long lds = 4LL * (gray_rt_plane_words(a.R, a.L, a.S) + GrayWord<GUIDE>::ENTRIES * kGrayCopies);
-    if (lds > kLdsBudget) return VIP_ERR_UNSUPPORTED_KSIZE;
-    constexpr auto kern = gray_rt_kernel<GUIDE, FMA>;
-    if (const int rc = ensure_lds<kern>(kLdsBudget)) return rc;
-    note_launch(reinterpret_cast<const void*>(kern));
-    const int tiles_y = (a.out_rows + kGrayRtWaves * 4 - 1) / (kGrayRtWaves * 4);
-    const long long tiles = (long long)a.tiles_x * tiles_y;
-    if (tiles == 0) return 0;
-    if (tiles > 0x7fffffffLL) return VIP_ERR_INVALID_ARGUMENT;
-    launch(kern, dim3((unsigned)tiles), dim3(kGrayRtWaves * 64), (uint32_t)lds, stream, a);
-    return (int)hipGetLastError();
+    if (const int rc = rt_prepare(a)) return rc;
+    const long long lds = 4LL * (rt_plane_words(a.R, a.L, a.S) + GrayWord<GUIDE>::ENTRIES * kGrayCopies);
+    return launch_rt_tiles<gray_rt_kernel<GUIDE, FMA>>(a, lds, stream);
 }
 
 int launch_gray_rt(const RtArgs& a, int guide_channels, bool fma, hipStream_t s) {

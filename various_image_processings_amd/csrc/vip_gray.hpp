@@ -1,10 +1,11 @@
 // What the single-channel (8-bit gray) kernels share (vip_gray.hip: bilateral and joint
 // bilateral; vip_gray_adaptive.hip: adaptive bilateral): the plane word of a pixel, the tile
-// loaders, the byte-exact store and the runtime-radius kernels' tile geometry.
+// loaders, the byte-exact store, the two forms of a tap's colour-LUT index (GraySad,
+// GrayAdaptiveDist) and the tap loop of one tile row of the radius-specialised kernels
+// (gray_row_taps). The runtime-radius kernels' tile geometry and launch are vip_rt.hpp's.
 #pragma once
 
-#include "vip_launch.hpp"
-#include "vip_stencil.hpp"
+#include "vip_rt.hpp"
 
 namespace vip {
 
@@ -137,21 +138,81 @@ __device__ __forceinline__ void store_gray(const A& a, int oy, int x, const uint
         if (x + i < a.width) p[i] = (uint8_t)o[i];
 }
 
-// ---- the runtime-radius kernels' tile
-constexpr int kGrayRtP = 4;                // outputs per thread
-constexpr int kGrayRtTW = 16 * kGrayRtP;   // tile width in pixels
-constexpr int kGrayRtWaves = 16;           // 64 tile rows
+// ---- a tap's colour-LUT index d, in two forms. Each is a plane-word reading (guide(w): what
+// the index is formed from; source(w): the neighbour's float) plus index(g, nf, i): d of the
+// neighbour with guide word g and float nf against the thread's output i.
+constexpr int kGrayAdaEntries = 512;  // the adaptive form's int(dist) <= 510
 
-// LDS words of the tile plane: (64 + 2R) rows x S words, + a zeroed pad when the apron is
-// narrower than the one-block over-read of the last row (R = 0 only)
-__host__ __device__ constexpr int gray_rt_plane_words(int R, int L, int S) {
-    return (kGrayRtWaves * 4 + 2 * R) * S + (L < 4 ? 8 : 0);
+// bilateral / joint bilateral: the sum of absolute byte differences of the guide words
+template <int GUIDE, int P>
+struct GraySad : GrayWord<GUIDE> {
+    uint32_t ctr[P];  // the outputs' centre guide words
+    __device__ __forceinline__ uint32_t index(uint32_t g, float, int i) const {
+        return __builtin_amdgcn_sad_u8(g, ctr[i], 0u);
+    }
+};
+// adaptive: |(n - c) - o| on the plain plane word, c the centre and o = c - box mean
+template <int P>
+struct GrayAdaptiveDist {
+    static constexpr int ENTRIES = kGrayAdaEntries;
+    float cf[P], of[P];
+    __device__ __forceinline__ static uint32_t guide(uint32_t w) { return w; }
+    __device__ __forceinline__ static float source(uint32_t w) { return (float)w; }
+    // (float)(n - c) == f_n - f_c exactly; int(dist) <= 510
+    __device__ __forceinline__ uint32_t index(uint32_t, float nf, int i) const {
+        return (uint32_t)__builtin_fabsf((nf - cf[i]) - of[i]);
+    }
+};
+
+// The tap loop of one tile row (row_taps' one-accumulator form): neighbour column j serves
+// output i at kx = j - L - i; per output the taps run in ascending kx.
+template <int HW, int L, int C0, int NC, bool FMA, int P, class DIST>
+__device__ __forceinline__ void gray_row_taps(const uint32_t* plane, int row_off, const float (&wsv)[HW + 1],
+                                              const char* lut, uint32_t lane4, const DIST& dist, float (&s)[P],
+                                              float (&sk)[P]) {
+    constexpr int D = kPipeDepth, NB = D + 1;
+    constexpr int J0 = L - HW, J1 = L + P - 1 + HW;
+    constexpr int LA = D + kRowLookahead;
+    static_assert(J0 >= 4 * C0 && J1 < 4 * (C0 + NC), "row chunk range");
+    auto chunk = [](int j) constexpr { return (j - 4 * C0) >> 2; };
+    constexpr int PRE = chunk(J0 + LA < J1 ? J0 + LA : J1);
+    RowStream<C0, NC, false> row(plane, plane, row_off);
+#pragma unroll
+    for (int q = 0; q <= PRE; ++q) row.load(q);
+    float wc[NB][P], nf[NB];
+    auto issue = [&](int j) {
+        const uint32_t w = row.guide(j - 4 * C0);
+        const uint32_t g = DIST::guide(w);
+        const int b = (j - J0) % NB;
+        nf[b] = DIST::source(w);
+#pragma unroll
+        for (int i = 0; i < P; ++i) {
+            const int kx = j - L - i;
+            if (kx < -HW || kx > HW) continue;
+            const uint32_t d = dist.index(g, nf[b], i);
+            wc[b][i] = *reinterpret_cast<const float*>(lut + ((d << 7) | lane4));
+        }
+    };
+#pragma unroll
+    for (int j = J0; j < J0 + D && j <= J1; ++j) issue(j);
+#pragma unroll
+    for (int j = J0; j <= J1; ++j) {
+        if (j + LA <= J1 && ((j + LA) & 3) == 0 && chunk(j + LA) > PRE) row.load(chunk(j + LA));
+        if (j + D <= J1) issue(j + D);
+        const int b = (j - J0) % NB;
+#pragma unroll
+        for (int i = 0; i < P; ++i) {
+            const int kx = j - L - i;
+            if (kx < -HW || kx > HW) continue;
+            const float w = wc[b][i] * wsv[kx < 0 ? -kx : kx];
+            if constexpr (FMA)
+                s[i] = __builtin_fmaf(nf[b], w, s[i]);
+            else
+                s[i] = s[i] + nf[b] * w;
+            sk[i] = sk[i] + w;
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    }
 }
-// S = 64 or 128: the 16-lane groups of a ds_read_b128 hit disjoint banks
-__host__ __device__ constexpr int gray_rt_stride(int L) { return kGrayRtTW + 2 * L <= 64 ? 64 : 128; }
-
-// The spatial table and the half-widths are read-only for the whole launch: read them
-// through the constant address space so the uniform loads become scalar loads.
-#define kconst __attribute__((address_space(4)))
 
 }  // namespace vip

@@ -32,13 +32,14 @@
 //       under VIP_PATH_RUNTIME); gray_rt_kernel's frame (one workgroup per 64 x 64 tile, 4
 //       outputs per thread, taps in blocks of 4 with exact zero weights outside the disc),
 //       per-thread sliding row sums and the IEEE quotient as stencil_rt_kernel's adaptive form.
+// The tap loop of a tile row is gray_kernel's (vip_gray.hpp gray_row_taps), with the
+// GrayAdaptiveDist index in place of the SAD.
 // Both numerics profiles (FMA: explicit __builtin_fmaf; otherwise mul + add, the build
 // has -ffp-contract=off) are instantiated here.
 #include "vip_gray.hpp"
 
 namespace vip {
 
-constexpr int kGrayAdaEntries = 512;  // int(dist) <= 510
 constexpr int kGrayAdaP = 8, kGrayAdaWaves = 16;
 
 // LDS words of the separable box sums' vertical pass: one u16 per tile row and plane column
@@ -60,56 +61,6 @@ constexpr bool gray_adaptive_vbox() {
     return (2 * R + 1) * 255 < 65536 && gray_adaptive_lds_bytes<R>() <= kLdsBudget;
 }
 static_assert(gray_adaptive_vbox<1>() && gray_adaptive_vbox<kMaxRadius>(), "separable box sums at every radius built");
-
-// The tap loop of one tile row (gray_row_taps' adaptive form): neighbour column j serves
-// output i at kx = j - L - i; per output the taps run in ascending kx.
-template <int HW, int L, int C0, int NC, bool FMA, int P>
-__device__ __forceinline__ void gray_adaptive_row_taps(const uint32_t* plane, int row_off, const float (&wsv)[HW + 1],
-                                                       const char* lut, uint32_t lane4, const float (&cf)[P],
-                                                       const float (&of)[P], float (&s)[P], float (&sk)[P]) {
-    constexpr int D = kPipeDepth, NB = D + 1;
-    constexpr int J0 = L - HW, J1 = L + P - 1 + HW;
-    constexpr int LA = D + kRowLookahead;
-    static_assert(J0 >= 4 * C0 && J1 < 4 * (C0 + NC), "row chunk range");
-    auto chunk = [](int j) constexpr { return (j - 4 * C0) >> 2; };
-    constexpr int PRE = chunk(J0 + LA < J1 ? J0 + LA : J1);
-    RowStream<C0, NC, false> row(plane, plane, row_off);
-#pragma unroll
-    for (int q = 0; q <= PRE; ++q) row.load(q);
-    float wc[NB][P], nf[NB];
-    auto issue = [&](int j) {
-        const int b = (j - J0) % NB;
-        nf[b] = (float)row.guide(j - 4 * C0);
-#pragma unroll
-        for (int i = 0; i < P; ++i) {
-            const int kx = j - L - i;
-            if (kx < -HW || kx > HW) continue;
-            // (float)(n - c) == f_n - f_c exactly; int(dist) <= 510
-            const uint32_t d = (uint32_t)__builtin_fabsf((nf[b] - cf[i]) - of[i]);
-            wc[b][i] = *reinterpret_cast<const float*>(lut + ((d << 7) | lane4));
-        }
-    };
-#pragma unroll
-    for (int j = J0; j < J0 + D && j <= J1; ++j) issue(j);
-#pragma unroll
-    for (int j = J0; j <= J1; ++j) {
-        if (j + LA <= J1 && ((j + LA) & 3) == 0 && chunk(j + LA) > PRE) row.load(chunk(j + LA));
-        if (j + D <= J1) issue(j + D);
-        const int b = (j - J0) % NB;
-#pragma unroll
-        for (int i = 0; i < P; ++i) {
-            const int kx = j - L - i;
-            if (kx < -HW || kx > HW) continue;
-            const float w = wc[b][i] * wsv[kx < 0 ? -kx : kx];
-            if constexpr (FMA)
-                s[i] = __builtin_fmaf(nf[b], w, s[i]);
-            else
-                s[i] = s[i] + nf[b] * w;
-            sk[i] = sk[i] + w;
-        }
-        __builtin_amdgcn_sched_barrier(0);
-    }
-}
 
 template <int R, bool FMA>
 __global__ __launch_bounds__(kGrayAdaWaves * 64) void gray_adaptive_kernel(const StencilArgs a) {
@@ -169,7 +120,7 @@ __global__ __launch_bounds__(kGrayAdaWaves * 64) void gray_adaptive_kernel(const
         }
         __syncthreads();
         if (ty0 + wave * G::RPW < a.out_rows) {  // wave-uniform: skip rows past the band
-            float cf[P], of[P];
+            GrayAdaptiveDist<P> dist;
             {
                 // ---- pass 1b (per thread): K-column windows of the vertical sums ----
                 constexpr int NCOLV = P + K - 1;
@@ -195,16 +146,16 @@ __global__ __launch_bounds__(kGrayAdaWaves * 64) void gray_adaptive_kernel(const
 #pragma unroll
                 for (int q = 0; q < P / 4; ++q) {
                     const uint4 v = c[q];
-                    cf[4 * q + 0] = (float)v.x;
-                    cf[4 * q + 1] = (float)v.y;
-                    cf[4 * q + 2] = (float)v.z;
-                    cf[4 * q + 3] = (float)v.w;
+                    dist.cf[4 * q + 0] = (float)v.x;
+                    dist.cf[4 * q + 1] = (float)v.y;
+                    dist.cf[4 * q + 2] = (float)v.z;
+                    dist.cf[4 * q + 3] = (float)v.w;
                 }
 #pragma unroll
                 for (int i = 0; i < P; ++i) {
                     // opaque to the optimiser (vip_adaptive.hip set_offsets): keeps n - c one v_sub_f32
-                    __asm__("" : "+v"(cf[i]));
-                    of[i] = cf[i] - div_exact(wsum[i], kk, rkk);  // offset = centre - box mean
+                    __asm__("" : "+v"(dist.cf[i]));
+                    dist.of[i] = dist.cf[i] - div_exact(wsum[i], kk, rkk);  // offset = centre - box mean
                 }
             }
             float s[P], sk[P];
@@ -222,7 +173,7 @@ __global__ __launch_bounds__(kGrayAdaWaves * 64) void gray_adaptive_kernel(const
                 float wsv[HW + 1];
 #pragma unroll
                 for (int k = 0; k <= HW; ++k) wsv[k] = ws[k];
-                gray_adaptive_row_taps<HW, G::L, C0, NC, FMA, P>(plane, row_off, wsv, lut_bytes, lane4, cf, of, s, sk);
+                gray_row_taps<HW, G::L, C0, NC, FMA, P>(plane, row_off, wsv, lut_bytes, lane4, dist, s, sk);
                 // pin the accumulators at the row's end (fence_accumulators)
 #pragma unroll
                 for (int i = 0; i < P; ++i) __asm__ volatile("" : "+v"(s[i]), "+v"(sk[i]));
@@ -277,12 +228,12 @@ struct GrayAdaRtWin {
 };
 
 template <bool FMA>
-__global__ __launch_bounds__(kGrayRtWaves * 64) void gray_adaptive_rt_kernel(const RtArgs a) {
-    constexpr int P = kGrayRtP, NT = kGrayRtWaves * 64, TH = kGrayRtWaves * 4;
+__global__ __launch_bounds__(kRtWaves * 64) void gray_adaptive_rt_kernel(const RtArgs a) {
+    constexpr int P = kRtP, NT = kRtWaves * 64, TH = kRtWaves * 4;
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     const int R = a.R, L = a.L, S = a.S;
     const int rows = TH + 2 * R;
-    const int pw = gray_rt_plane_words(R, L, S);
+    const int pw = rt_plane_words(R, L, S);
     uint32_t* const plane = lds;
     uint32_t* const lut = lds + pw;
 
@@ -292,7 +243,7 @@ __global__ __launch_bounds__(kGrayRtWaves * 64) void gray_adaptive_rt_kernel(con
     const int tx = lane & 15;
     const int ty = wave * 4 + (lane >> 4);
     const int tile = blockIdx.x;
-    const int tx0 = (tile % a.tiles_x) * kGrayRtTW, ty0 = (tile / a.tiles_x) * TH;
+    const int tx0 = (tile % a.tiles_x) * kRtTW, ty0 = (tile / a.tiles_x) * TH;
 
     // colour LUT: word d * 32 + c = color[d], d < 512
     for (int q = tid; q < kGrayAdaEntries * kGrayCopies / 4; q += NT) {
@@ -303,7 +254,7 @@ __global__ __launch_bounds__(kGrayRtWaves * 64) void gray_adaptive_rt_kernel(con
     // reads up to 4 words past its apron (weight 0), and a zero word's index against any
     // centre, int(|0 - 2c + mean|) <= 510, is still inside the table
     {
-        const int gpr = S / 4, valid = (kGrayRtTW + 2 * L) / 4;
+        const int gpr = S / 4, valid = (kRtTW + 2 * L) / 4;
         for (int q = tid; q < rows * gpr; q += NT) {
             const int r = q / gpr, gc = q - r * gpr;
             uint4 w = make_uint4(0u, 0u, 0u, 0u);
@@ -415,21 +366,9 @@ __global__ __launch_bounds__(kGrayRtWaves * 64) void gray_adaptive_rt_kernel(con
 
 template <bool FMA>
 static int launch_gray_adaptive_rt_f(RtArgs a, hipStream_t stream) {
-    if (a.R < 0 || a.R > kRtMaxRadius) return VIP_ERR_UNSUPPORTED_KSIZE;
-    a.L = round_up(a.R, 4);
-    a.S = gray_rt_stride(a.L);
-    a.tiles_x = (a.width + kGrayRtTW - 1) / kGrayRtTW;
-    const long long lds = 4LL * (gray_rt_plane_words(a.R, a.L, a.S) + kGrayAdaEntries * kGrayCopies);
-    if (lds > kLdsBudget) return VIP_ERR_UNSUPPORTED_KSIZE;
-    constexpr auto kern = gray_adaptive_rt_kernel<FMA>;
-    if (const int rc = ensure_lds<kern>(kLdsBudget)) return rc;
-    note_launch(reinterpret_cast<const void*>(kern));
-    const int tiles_y = (a.out_rows + kGrayRtWaves * 4 - 1) / (kGrayRtWaves * 4);
-    const long long tiles = (long long)a.tiles_x * tiles_y;
-    if (tiles == 0) return 0;
-    if (tiles > 0x7fffffffLL) return VIP_ERR_INVALID_ARGUMENT;
-    launch(kern, dim3((unsigned)tiles), dim3(kGrayRtWaves * 64), (uint32_t)lds, stream, a);
-    return (int)hipGetLastError();
+    if (const int rc = rt_prepare(a)) return rc;
+    const long long lds = 4LL * (rt_plane_words(a.R, a.L, a.S) + kGrayAdaEntries * kGrayCopies);
+    return launch_rt_tiles<gray_adaptive_rt_kernel<FMA>>(a, lds, stream);
 }
 
 int launch_gray_adaptive_rt(const RtArgs& a, bool fma, hipStream_t s) {

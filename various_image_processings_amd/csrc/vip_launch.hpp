@@ -65,8 +65,9 @@ struct StencilArgs {
     float ws[kWsStride * kWsStride];  // spatial LUT, |ky|-major, in the kernarg segment (scalar loads)
 };
 
-// Runtime-radius kernel (vip_stencil_rt.hip): radius 0 and the radii above the
-// templated set, up to the reference's largest (bilateral ksize 65).
+// Runtime-radius kernels (vip_stencil_rt.hip and the one-channel ones; their shared frame and
+// its launch helpers rt_prepare / launch_rt_tiles: vip_rt.hpp): radius 0 and the radii above
+// the templated set, up to the reference's largest (bilateral ksize 65).
 constexpr int kRtMaxRadius = 32;
 
 struct RtArgs {

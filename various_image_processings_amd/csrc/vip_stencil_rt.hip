@@ -25,21 +25,11 @@
 //   * adaptive: the k x k box sums (the window mean, src/adaptive_bilateral_filter_impl.cu:
 //     79-93) are per-thread sliding row sums over the plane, exact integers; the mean is
 //     the IEEE quotient by k^2 as in the reference.
-#include "vip_launch.hpp"
-#include "vip_stencil.hpp"
+// The tile geometry and the launch are vip_rt.hpp's, shared with the one-channel
+// runtime-radius kernels (vip_gray.hip, vip_gray_adaptive.hip).
+#include "vip_rt.hpp"
 
 namespace vip {
-
-constexpr int kRtP = 4;           // outputs per thread
-constexpr int kRtTW = 16 * kRtP;  // tile width in pixels
-constexpr int kRtWaves = 16;
-
-// LDS words of one tile plane (+ a zeroed pad when the apron is narrower than the
-// one-block over-read of the last row, i.e. only at R = 0)
-__host__ __device__ constexpr int rt_plane_words(int R, int L, int S, int waves) {
-    return (waves * 4 + 2 * R) * S + (L < 4 ? 8 : 0);
-}
-__host__ __device__ constexpr int rt_stride(int L) { return kRtTW + 2 * L <= 64 ? 64 : 128; }
 
 // One 4-pixel group of image row sy starting at column x (clamped to the image), as
 // RGBX words: three dword loads when interior and aligned, clamped bytes otherwise.
@@ -80,10 +70,6 @@ struct RtWin {
     }
 };
 
-// The spatial table and the half-widths are read-only for the whole launch: read them
-// through the constant address space so the uniform loads become scalar loads.
-#define kconst __attribute__((address_space(4)))
-
 template <int COPIES, bool JOINT, bool FMA, bool ADAPTIVE>
 __global__ __launch_bounds__(kRtWaves * 64) void stencil_rt_kernel(const RtArgs a) {
     constexpr int P = kRtP, NT = kRtWaves * 64, TH = kRtWaves * 4;
@@ -91,7 +77,7 @@ __global__ __launch_bounds__(kRtWaves * 64) void stencil_rt_kernel(const RtArgs 
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     const int R = a.R, L = a.L, S = a.S;
     const int rows = TH + 2 * R;
-    const int pw = rt_plane_words(R, L, S, kRtWaves);
+    const int pw = rt_plane_words(R, L, S);
     uint32_t* const gplane = lds;
     uint32_t* const splane = JOINT ? lds + pw : lds;
     uint32_t* const lut = lds + (JOINT ? 2 : 1) * pw;
@@ -267,46 +253,22 @@ __global__ __launch_bounds__(kRtWaves * 64) void stencil_rt_kernel(const RtArgs 
     store_px(a, ty0 + ty, tx0 + tx * P, o);
 }
 
-template <int COPIES, bool JOINT, bool FMA, bool ADAPTIVE>
-static int launch_rt_c(const RtArgs& a, int lds, hipStream_t stream) {
-    constexpr auto kern = stencil_rt_kernel<COPIES, JOINT, FMA, ADAPTIVE>;
-    if (const int rc = ensure_lds<kern>(kLdsBudget)) return rc;
-    note_launch(reinterpret_cast<const void*>(kern));
-    const int tiles_y = (a.out_rows + kRtWaves * 4 - 1) / (kRtWaves * 4);
-    const long long tiles = (long long)a.tiles_x * tiles_y;
-    if (tiles == 0) return 0;
-    if (tiles > 0x7fffffffLL) return VIP_ERR_INVALID_ARGUMENT;
-    launch(kern, dim3((unsigned)tiles), dim3(kRtWaves * 64), lds, stream, a);
-    return (int)hipGetLastError();
-}
-
-// LDS bytes of the runtime kernel for radius R with `copies` LUT copies, or 0 if it
-// does not fit the CU.
-static int rt_lds_bytes(int R, bool joint, bool adaptive, int copies) {
-    const int L = round_up(R, 4);
-    const int S = rt_stride(L);
-    const long long bytes = 4LL * (joint ? 2 : 1) * rt_plane_words(R, L, S, kRtWaves) +
-                            4LL * (adaptive ? 1536 : 768) * copies;
-    return bytes <= kLdsBudget ? (int)bytes : 0;
+// LDS bytes of the runtime kernel for a prepared launch with `copies` LUT copies
+static long long rt_lds_bytes(const RtArgs& a, bool joint, bool adaptive, int copies) {
+    return 4LL * (joint ? 2 : 1) * rt_plane_words(a.R, a.L, a.S) + 4LL * (adaptive ? 1536 : 768) * copies;
 }
 
 template <bool FMA>
 static int launch_rt(RtArgs a, bool joint, bool adaptive, hipStream_t stream) {
-    if (a.R < 0 || a.R > kRtMaxRadius) return VIP_ERR_UNSUPPORTED_KSIZE;
-    a.L = round_up(a.R, 4);
-    a.S = rt_stride(a.L);
-    a.tiles_x = (a.width + kRtTW - 1) / kRtTW;
-    if (adaptive) {
-        const int lds = rt_lds_bytes(a.R, false, true, 16);
-        return lds ? launch_rt_c<16, false, FMA, true>(a, lds, stream) : VIP_ERR_UNSUPPORTED_KSIZE;
+    if (const int rc = rt_prepare(a)) return rc;
+    if (adaptive)
+        return launch_rt_tiles<stencil_rt_kernel<16, false, FMA, true>>(a, rt_lds_bytes(a, false, true, 16), stream);
+    if (joint) {  // two planes: 32 LUT copies while they fit the CU
+        if (const long long lds = rt_lds_bytes(a, true, false, 32); lds <= kLdsBudget)
+            return launch_rt_tiles<stencil_rt_kernel<32, true, FMA, false>>(a, lds, stream);
+        return launch_rt_tiles<stencil_rt_kernel<16, true, FMA, false>>(a, rt_lds_bytes(a, true, false, 16), stream);
     }
-    if (joint) {
-        if (const int lds = rt_lds_bytes(a.R, true, false, 32)) return launch_rt_c<32, true, FMA, false>(a, lds, stream);
-        const int lds = rt_lds_bytes(a.R, true, false, 16);
-        return lds ? launch_rt_c<16, true, FMA, false>(a, lds, stream) : VIP_ERR_UNSUPPORTED_KSIZE;
-    }
-    const int lds = rt_lds_bytes(a.R, false, false, 32);
-    return lds ? launch_rt_c<32, false, FMA, false>(a, lds, stream) : VIP_ERR_UNSUPPORTED_KSIZE;
+    return launch_rt_tiles<stencil_rt_kernel<32, false, FMA, false>>(a, rt_lds_bytes(a, false, false, 32), stream);
 }
 
 int launch_stencil_rt(const RtArgs& a, bool joint, bool adaptive, bool fma, hipStream_t stream) {
