@@ -38,6 +38,14 @@ public:
     void joint_bilateral_filter_c1(const std::uint8_t* const d_src, const std::uint8_t* const d_guide,
                                    const int guide_channels, std::uint8_t* const d_dst, void* stream) const;
 
+    // Additive f32 form, no reference counterpart (include/vip.h vip_joint_bilateral_run_f32): a
+    // dense width x height float source and destination under a dense gray (guide_channels 1) or
+    // interleaved 3-channel (guide_channels 3) 8-bit guide. Blocking, and with a stream non-blocking.
+    void joint_bilateral_filter_f32(const float* const d_src, const std::uint8_t* const d_guide,
+                                    const int guide_channels, float* const d_dst) const;
+    void joint_bilateral_filter_f32(const float* const d_src, const std::uint8_t* const d_guide,
+                                    const int guide_channels, float* const d_dst, void* stream) const;
+
 protected:
     class Impl;  // defined in bilateral_filter_impl.cuh (test drivers reach it through impl_)
     std::unique_ptr<Impl> impl_;

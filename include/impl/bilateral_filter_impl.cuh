@@ -33,6 +33,12 @@ public:
     void joint_bilateral_filter_c1(const std::uint8_t* const d_src, const std::uint8_t* const d_guide,
                                    const int guide_channels, std::uint8_t* const d_dst, void* stream) const;
 
+    // f32 source under an 8-bit guide (include/cuda/bilateral_filter.hpp)
+    void joint_bilateral_filter_f32(const float* const d_src, const std::uint8_t* const d_guide,
+                                    const int guide_channels, float* const d_dst) const;
+    void joint_bilateral_filter_f32(const float* const d_src, const std::uint8_t* const d_guide,
+                                    const int guide_channels, float* const d_dst, void* stream) const;
+
     vip_bilateral_t handle() const { return handle_; }
 
 private:

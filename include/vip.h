@@ -180,6 +180,51 @@ int vip_joint_bilateral_run_c1(vip_bilateral_t h, const uint8_t* d_src, size_t s
 int vip_bilateral_run_rows_c1(vip_bilateral_t h, const uint8_t* d_src, size_t src_pitch, const uint8_t* d_guide,
                               size_t guide_pitch, int guide_channels, uint8_t* d_dst, size_t dst_pitch, int out_rows,
                               int src_row0, int row_lo, int row_hi, void* stream);
+/* ---- joint bilateral of an f32 one-channel source under an 8-bit guide (no counterpart in the
+ * reference's API; OpenCV's ximgproc::jointBilateralFilter takes this pair): a depth, disparity,
+ * flow, matte or cost field f smoothed under a gray (guide_channels 1) or interleaved 3-channel
+ * (guide_channels 3) 8-bit image G. The handle is the same vip_bilateral_t, radius ksize / 2,
+ * with its spatial LUT ws and its 768-entry colour LUT wc; borders replicate. Per output pixel
+ * the taps run in row-major order over the k x k square:
+ *   d    = |G_n - G_c|            (guide_channels 1; reaches LUT entries 0..255)
+ *        = |dB| + |dG| + |dR|     (guide_channels 3; 0..765)
+ *   w    = ws[ky,kx] * wc[d]      (ws is exactly 0 outside the disc)
+ *   s    = fmaf(f_n, w, s)        VIP_NUMERICS_CUDA
+ *   s    = s + f_n * w            VIP_NUMERICS_CPP (two roundings)
+ *   sumk = sumk + w
+ *   dst  = s / sumk               IEEE binary32 division, no rounding to integer, no clamp
+ * Arithmetic is binary32 with gradual underflow: the build's -O3 -ffp-contract=off leaves the
+ * kernels in denormal mode 3 (.amdhsa_float_denorm_mode_32 3 in every kernel descriptor).
+ * sumk >= 1 always (the centre tap has w = 1).
+ * Domain: every source value must be finite. For finite input the result equals the definition
+ * bit for bit, in both profiles and on both kernel paths. With an Inf or NaN in the source the
+ * values are unspecified (the runtime-radius kernel also multiplies out-of-disc neighbours by an
+ * exact zero weight, a no-op only for finite neighbours), but such a call cannot fault:
+ * every address comes from the guide. Sums that overflow give +-Inf, as in the definition.
+ * Tie to the 8-bit form: for f == (float)g with a gray u8 frame g, u8(dst + 0.5f) is
+ * vip_joint_bilateral_run_c1 on g, bit for bit (s and sumk are the same floats).
+ * ksize 1..47 odd (VIP_ERR_UNSUPPORTED_KSIZE on a larger handle); ksize 1 copies f.
+ * Pitches are in bytes. d_src and d_dst bases and pitches must be multiples of 4
+ * (VIP_ERR_INVALID_ARGUMENT otherwise); any such value works: the kernels take 16-byte loads
+ * and stores only where base and pitch are multiples of 16, dword accesses otherwise. d_guide
+ * may have any base and pitch. No byte of d_dst at column >= width or row >= out_rows is
+ * written. VIP_ERR_INVALID_ARGUMENT: null handle or pointer (a null guide too: there is no
+ * plain f32 form), a bad band, guide_channels not 1 or 3; VIP_ERR_ALIASING: d_dst equals d_src
+ * or d_guide. One launch per call, no device allocation. Kernels under VIP_PATH_AUTO:
+ * vip::joint_f32_kernel<R, GUIDE, FMA> for radius 1..15 (gray guide: 32 LUT copies, 16-wave
+ * workgroups and 128 x 64 tiles up to radius 12, 12 waves and 128 x 48 tiles for radius 13..15;
+ * 3-channel guide: 16 LUT copies, 16 waves up to radius 9, 12 waves for radius 10..15),
+ * vip::joint_f32_rt_kernel<GUIDE, FMA> (64 x 64 tiles, the same LUTs) for radius 0 and
+ * 16..23; under VIP_PATH_RUNTIME joint_f32_rt_kernel for every radius. The launch log and
+ * vip_kernel_timing_* see them; vip_bilateral_set_waves / _set_wide / _set_frames_in_flight do
+ * not apply. The _rows form takes a row band as vip_bilateral_run_rows_c1. */
+int vip_joint_bilateral_run_f32(vip_bilateral_t h, const float* d_src, size_t src_pitch, const uint8_t* d_guide,
+                                size_t guide_pitch, int guide_channels, float* d_dst, size_t dst_pitch,
+                                void* stream);
+int vip_joint_bilateral_run_rows_f32(vip_bilateral_t h, const float* d_src, size_t src_pitch,
+                                     const uint8_t* d_guide, size_t guide_pitch, int guide_channels, float* d_dst,
+                                     size_t dst_pitch, int out_rows, int src_row0, int row_lo, int row_hi,
+                                     void* stream);
 /* Tuning knob, process-wide (no reference counterpart): waves per workgroup of the plain
  * bilateral kernel for radius <= 8. 0 (default) = chosen per launch from the frame's
  * tile count (small frames take 8 or 4 waves and smaller tiles so more CUs work);

@@ -624,6 +624,43 @@ int vip_joint_bilateral_run_c1(vip_bilateral_t h, const uint8_t* d_src, size_t s
                                      h->height, 0, 0, h->height, stream);
 }
 
+// ---- f32 one-channel source under an 8-bit guide (vip_joint_f32.hip): the same band, handle and
+// tables; the float pointers travel as the band's byte pointers, and the flags that pick the
+// wide loads and stores take the meanings the f32 kernels give them
+int vip_joint_bilateral_run_rows_f32(vip_bilateral_t h, const float* d_src, size_t src_pitch, const uint8_t* d_guide,
+                                     size_t guide_pitch, int guide_channels, float* d_dst, size_t dst_pitch,
+                                     int out_rows, int src_row0, int row_lo, int row_hi, void* stream) {
+    if (!h || !d_guide) return VIP_ERR_INVALID_ARGUMENT;
+    const RowBand b{reinterpret_cast<const uint8_t*>(d_src), src_pitch, d_guide, guide_pitch,
+                    reinterpret_cast<uint8_t*>(d_dst), dst_pitch, out_rows, src_row0, row_lo, row_hi};
+    if (const int rc = check_band(h->height, b)) return rc;
+    if (guide_channels != 1 && guide_channels != 3) return VIP_ERR_INVALID_ARGUMENT;
+    if (!is_aligned(d_src, src_pitch, 4) || !is_aligned(d_dst, dst_pitch, 4)) return VIP_ERR_INVALID_ARGUMENT;
+    if (h->ksize > kMaxKsizeJoint) return VIP_ERR_UNSUPPORTED_KSIZE;
+    const int aligned = (is_aligned(d_guide, guide_pitch, 4) ? kF32GuideWords : 0) |
+                        (is_aligned(d_src, src_pitch, 16) ? kF32SrcVec : 0);
+    const int dst_aligned = is_aligned(d_dst, dst_pitch, 16);
+    const bool fma = h->numerics == VIP_NUMERICS_CUDA;
+    if (use_runtime_kernel(h->radius)) {
+        RtArgs a = rt_args(*h, b);
+        a.aligned = aligned;
+        a.dst_aligned = dst_aligned;
+        return launch_joint_f32_rt(a, guide_channels, fma, (hipStream_t)stream);
+    }
+    StencilArgs a = stencil_args(*h, b);
+    a.aligned = aligned;
+    a.dst_aligned = dst_aligned;
+    return launch_joint_f32(h->radius, guide_channels, fma, a, (hipStream_t)stream);
+}
+
+int vip_joint_bilateral_run_f32(vip_bilateral_t h, const float* d_src, size_t src_pitch, const uint8_t* d_guide,
+                                size_t guide_pitch, int guide_channels, float* d_dst, size_t dst_pitch,
+                                void* stream) {
+    if (!h) return VIP_ERR_INVALID_ARGUMENT;
+    return vip_joint_bilateral_run_rows_f32(h, d_src, src_pitch, d_guide, guide_pitch, guide_channels, d_dst,
+                                            dst_pitch, h->height, 0, 0, h->height, stream);
+}
+
 // The frames of a *_run_rows_batch call, or a run of them
 struct Batch {
     int n;

@@ -79,6 +79,19 @@ void CudaBilateralFilter::Impl::joint_bilateral_filter_c1(const std::uint8_t* co
                                           guide_channels, d_dst, pitch, stream));
 }
 
+void CudaBilateralFilter::Impl::joint_bilateral_filter_f32(const float* const d_src, const std::uint8_t* const d_guide,
+                                                           const int guide_channels, float* const d_dst) const {
+    joint_bilateral_filter_f32(d_src, d_guide, guide_channels, d_dst, nullptr);
+}
+void CudaBilateralFilter::Impl::joint_bilateral_filter_f32(const float* const d_src, const std::uint8_t* const d_guide,
+                                                           const int guide_channels, float* const d_dst,
+                                                           void* stream) const {
+    const size_t pitch = (size_t)width_;
+    VIP_REPORT(vip_joint_bilateral_run_f32(handle_, d_src, pitch * sizeof(float), d_guide,
+                                           pitch * (size_t)(guide_channels == 3 ? 3 : 1), guide_channels, d_dst,
+                                           pitch * sizeof(float), stream));
+}
+
 CudaBilateralFilter::CudaBilateralFilter(const int width, const int height, const int ksize, const float sigma_space,
                                          const float sigma_color)
     : impl_(std::make_unique<Impl>(width, height, ksize, sigma_space, sigma_color)) {}
@@ -122,6 +135,16 @@ void CudaBilateralFilter::joint_bilateral_filter_c1(const std::uint8_t* const d_
                                                     const int guide_channels, std::uint8_t* const d_dst,
                                                     void* stream) const {
     impl_->joint_bilateral_filter_c1(d_src, d_guide, guide_channels, d_dst, stream);
+}
+void CudaBilateralFilter::joint_bilateral_filter_f32(const float* const d_src, const std::uint8_t* const d_guide,
+                                                     const int guide_channels, float* const d_dst) const {
+    impl_->joint_bilateral_filter_f32(d_src, d_guide, guide_channels, d_dst);
+    VIP_REPORT(vip_device_synchronize());
+}
+void CudaBilateralFilter::joint_bilateral_filter_f32(const float* const d_src, const std::uint8_t* const d_guide,
+                                                     const int guide_channels, float* const d_dst,
+                                                     void* stream) const {
+    impl_->joint_bilateral_filter_f32(d_src, d_guide, guide_channels, d_dst, stream);
 }
 
 // ------------------------------------------------------------ CudaAdaptiveBilateralFilter

@@ -101,6 +101,14 @@ int launch_gray_rt(const RtArgs& a, int guide_channels, bool fma, hipStream_t s)
 // vip_gray_adaptive.hip: the one-channel adaptive filter; radius 1..15 / runtime radius
 int launch_gray_adaptive(int radius, bool fma, const StencilArgs& a, hipStream_t s);
 int launch_gray_adaptive_rt(const RtArgs& a, bool fma, hipStream_t s);
+// vip_joint_f32.hip: f32 one-channel source and destination under an 8-bit guide (guide_channels
+// 1 or 3); radius 1..15 / runtime radius 0..23. src and dst carry the float pointers, pitches in
+// bytes; `aligned` is a set of the bits below and dst_aligned means base and pitch are 16-byte
+// aligned (float4 stores), both set by the entry point (vip_joint_bilateral_run_rows_f32)
+constexpr int kF32GuideWords = 1;  // guide base and pitch are 4-byte aligned -> dword guide loads
+constexpr int kF32SrcVec = 2;      // source base and pitch are 16-byte aligned -> float4 loads
+int launch_joint_f32(int radius, int guide_channels, bool fma, const StencilArgs& a, hipStream_t s);
+int launch_joint_f32_rt(const RtArgs& a, int guide_channels, bool fma, hipStream_t s);
 int launch_gradient_u8(const uint8_t* src, float* dst, int width, int height, int ch, hipStream_t stream);
 int launch_gradient_f32(const float* src, float* dst, int width, int height, int ch, bool fma, hipStream_t stream);
 int launch_blur_rtv(const uint8_t* img, const float* mag, float* blurred, float* rtv, int width, int height,

@@ -6,7 +6,9 @@ yuyuyu-bot/various_image_processings:
 * ``CudaBilateralFilter(width, height, ksize=9, sigma_space=10., sigma_color=30.)``
   with ``bilateral_filter(d_src, d_dst)`` and ``joint_bilateral_filter(d_src, d_guide, d_dst)``
   (include/cuda/bilateral_filter.hpp:9-24), and their one-channel forms ``bilateral_filter_c1(d_src,
-  d_dst)`` / ``joint_bilateral_filter_c1(d_src, d_guide, guide_channels, d_dst)`` (no reference counterpart)
+  d_dst)`` / ``joint_bilateral_filter_c1(d_src, d_guide, guide_channels, d_dst)`` (no reference counterpart),
+  and ``joint_bilateral_filter_f32(d_src, d_guide, guide_channels, d_dst)``: a float32 one-channel source
+  and destination under an 8-bit guide (no reference counterpart)
 * ``CudaAdaptiveBilateralFilter(...).execute(d_src, d_dst)`` (adaptive_bilateral_filter.hpp:9-19), and its
   one-channel form ``execute_c1(d_src, d_dst)`` (no reference counterpart)
 * ``CudaBilateralTextureFilter(width, height, ksize=9, nitr=3).execute(d_src, d_dst)``
@@ -206,9 +208,9 @@ class _BilateralImpl(_Handle):
     # single-channel (8-bit gray) forms, include/vip.h vip_bilateral_run_c1: d_src and d_dst are
     # width * height bytes; the guide is gray (guide_channels 1) or interleaved 3-channel (3)
     @staticmethod
-    def _guide_channels(guide_channels) -> int:
+    def _guide_channels(guide_channels, func="vip_joint_bilateral_run_c1") -> int:
         if int(guide_channels) not in (1, 3):
-            raise VipError("vip_joint_bilateral_run_c1", _lib.VIP_ERR_INVALID_ARGUMENT)
+            raise VipError(func, _lib.VIP_ERR_INVALID_ARGUMENT)
         return int(guide_channels)
 
     def bilateral_filter_c1(self, d_src, d_dst, stream=None):
@@ -229,6 +231,22 @@ class _BilateralImpl(_Handle):
         call("vip_bilateral_run_rows_c1", self._h, _ptr(d_src, p * int(row_hi)), p, g, p * gch, gch,
              _ptr(d_dst, p * int(out_rows)), p, int(out_rows), int(src_row0), int(row_lo), int(row_hi),
              _stream(stream))
+
+    # f32 one-channel source under an 8-bit guide, include/vip.h vip_joint_bilateral_run_f32: d_src
+    # and d_dst are width * height float32; the guide is gray (guide_channels 1) or 3-channel (3)
+    def joint_bilateral_filter_f32(self, d_src, d_guide, guide_channels, d_dst, stream=None):
+        gch = self._guide_channels(guide_channels, "vip_joint_bilateral_run_f32")
+        p, n = self.width, self.width * self.height
+        call("vip_joint_bilateral_run_f32", self._h, _ptr(d_src, 4 * n, dtype="float32"), 4 * p,
+             _ptr(d_guide, n * gch), p * gch, gch, _ptr(d_dst, 4 * n, dtype="float32"), 4 * p, _stream(stream))
+
+    def run_rows_f32(self, d_src, d_guide, guide_channels, d_dst, out_rows, src_row0, row_lo, row_hi, stream=None):
+        """run_rows for an f32 source under an 8-bit guide (include/vip.h vip_joint_bilateral_run_rows_f32)."""
+        gch = self._guide_channels(guide_channels, "vip_joint_bilateral_run_rows_f32")
+        p = self.width
+        call("vip_joint_bilateral_run_rows_f32", self._h, _ptr(d_src, 4 * p * int(row_hi), dtype="float32"), 4 * p,
+             _ptr(d_guide, p * gch * int(row_hi)), p * gch, gch, _ptr(d_dst, 4 * p * int(out_rows), dtype="float32"),
+             4 * p, int(out_rows), int(src_row0), int(row_lo), int(row_hi), _stream(stream))
 
     def run_rows_batch(self, d_srcs, d_dsts, out_rows, src_row0, row_lo, row_hi, free_cus=0, stream=None):
         """run_rows over several frames of the same geometry, up to 6 per launch
@@ -268,6 +286,11 @@ class CudaBilateralFilter:
 
     def joint_bilateral_filter_c1(self, d_src, d_guide, guide_channels, d_dst):
         self.impl_.joint_bilateral_filter_c1(d_src, d_guide, guide_channels, d_dst)
+        device_synchronize()
+
+    def joint_bilateral_filter_f32(self, d_src, d_guide, guide_channels, d_dst):
+        """float32 one-channel source under an 8-bit guide (include/vip.h vip_joint_bilateral_run_f32)."""
+        self.impl_.joint_bilateral_filter_f32(d_src, d_guide, guide_channels, d_dst)
         device_synchronize()
 
 
