@@ -1,8 +1,12 @@
-// What the single-channel (8-bit gray) kernels share (vip_gray.hip: bilateral and joint
-// bilateral; vip_gray_adaptive.hip: adaptive bilateral): the plane word of a pixel, the tile
-// loaders, the byte-exact store, the two forms of a tap's colour-LUT index (GraySad,
-// GrayAdaptiveDist) and the tap loop of one tile row of the radius-specialised kernels
-// (gray_row_taps). The runtime-radius kernels' tile geometry and launch are vip_rt.hpp's.
+// What the one-channel kernels share (vip_gray.hip: bilateral and joint bilateral;
+// vip_gray_adaptive.hip: adaptive bilateral; vip_joint_f32.hip: joint bilateral of an f32 source,
+// a guide and a float plane): the plane word of a pixel, the guide and tile loaders and the
+// register-staged tile prefetch (Guide4, GrayGroup, C1Prefetch), the byte-exact store, the forms
+// of a tap's colour-LUT index (GraySad, GrayAdaptiveDist; F32Sad is vip_joint_f32.hip's) and, for
+// the radius-specialised kernels, the tap loop of one tile row (gray_row_taps) and the
+// one-plane kernels' row around it (gray_tile_row). The runtime-radius kernels' tile geometry
+// and launch are vip_rt.hpp's, the radius dispatch and the persistent launch vip_launch.hpp's
+// (dispatch_radius, launch_c1_tiles).
 #pragma once
 
 #include "vip_rt.hpp"
@@ -16,10 +20,13 @@ struct GrayWord {
     static constexpr uint32_t MASK = GUIDE == 3 ? 0xffffffu : 0xffu;   // the guide's bytes
     static constexpr int SHIFT = GUIDE == 3 ? 24 : (GUIDE == 1 ? 8 : 0);  // the source's byte
     static constexpr int ENTRIES = GUIDE == 3 ? 768 : 256;              // colour-LUT entries d can reach
+    static constexpr bool TWO = false;     // one plane: the word holds guide and source
+    static constexpr int LUT_SHIFT = 7;    // LUT byte address: d << 7 | 4 * copy (kGrayCopies)
     __device__ __forceinline__ static uint32_t guide(uint32_t w) { return GUIDE == 0 ? w : (w & MASK); }
     __device__ __forceinline__ static float source(uint32_t w) { return (float)((w >> SHIFT) & 0xffu); }
 };
 constexpr int kGrayCopies = 32;
+static_assert(kGrayCopies * 4 == 1 << GrayWord<0>::LUT_SHIFT, "LUT address: d << 7");
 
 // 4 gray pixels of one image row from column x (columns clamped to the image), pixel k in
 // byte k: one dword load when the group is interior and the row is dword aligned.
@@ -29,19 +36,16 @@ __device__ __forceinline__ uint32_t load_gray4(const uint8_t* row, int x, int wi
            ((uint32_t)row[clampi(x + 2, 0, width - 1)] << 16) | ((uint32_t)row[clampi(x + 3, 0, width - 1)] << 24);
 }
 
-// One 4-pixel group as loaded from HBM (the source dword and the guide's 1 or 3 dwords),
-// and as the 4 plane words it becomes.
+// The guide's 4 pixels of one image row from column x (columns clamped to the image) as its 1
+// (g0) or 3 dwords: dword loads when the group is interior and the row is dword aligned.
 template <int GUIDE>
-struct GrayGroup {
-    uint32_t s, g0, g1, g2;
+struct Guide4 {
+    uint32_t g0, g1, g2;
 
-    __device__ __forceinline__ void load(const uint8_t* src, long long src_pitch, const uint8_t* guide,
-                                         long long guide_pitch, int sy, int x, int width, int aligned) {
-        s = load_gray4(src + (long long)sy * src_pitch, x, width, aligned);
+    __device__ __forceinline__ void load(const uint8_t* row, int x, int width, int aligned) {
         g0 = g1 = g2 = 0u;
-        if constexpr (GUIDE == 1) g0 = load_gray4(guide + (long long)sy * guide_pitch, x, width, aligned);
+        if constexpr (GUIDE == 1) g0 = load_gray4(row, x, width, aligned);
         if constexpr (GUIDE == 3) {
-            const uint8_t* row = guide + (long long)sy * guide_pitch;
             if (aligned && x >= 0 && x + 3 < width) {
                 const uint32_t* w = reinterpret_cast<const uint32_t*>(row + 3 * x);
                 g0 = w[0];
@@ -58,7 +62,21 @@ struct GrayGroup {
             }
         }
     }
+};
 
+// One 4-pixel group as loaded from HBM (the source dword and the guide's 1 or 3 dwords),
+// and as the 4 plane words it becomes.
+template <int GUIDE>
+struct GrayGroup {
+    static constexpr bool TWO = false;  // one plane
+    uint32_t s;
+    Guide4<GUIDE> g;
+
+    __device__ __forceinline__ void load(const uint8_t* src, long long src_pitch, const uint8_t* guide,
+                                         long long guide_pitch, int sy, int x, int width, int aligned) {
+        s = load_gray4(src + (long long)sy * src_pitch, x, width, aligned);
+        g.load(guide + (long long)sy * guide_pitch, x, width, aligned);
+    }
     __device__ __forceinline__ uint4 words() const {
         uint4 r;
         if constexpr (GUIDE == 0) {
@@ -67,12 +85,12 @@ struct GrayGroup {
             r.z = (s >> 16) & 0xffu;
             r.w = s >> 24;
         } else if constexpr (GUIDE == 1) {
-            r.x = (g0 & 0xffu) | ((s & 0xffu) << 8);
-            r.y = ((g0 >> 8) & 0xffu) | (s & 0xff00u);
-            r.z = ((g0 >> 16) & 0xffu) | ((s >> 8) & 0xff00u);
-            r.w = (g0 >> 24) | ((s >> 16) & 0xff00u);
+            r.x = (g.g0 & 0xffu) | ((s & 0xffu) << 8);
+            r.y = ((g.g0 >> 8) & 0xffu) | (s & 0xff00u);
+            r.z = ((g.g0 >> 16) & 0xffu) | ((s >> 8) & 0xff00u);
+            r.w = (g.g0 >> 24) | ((s >> 16) & 0xff00u);
         } else {
-            const uint4 u = unpack_rgb4(g0, g1, g2);
+            const uint4 u = unpack_rgb4(g.g0, g.g1, g.g2);
             r.x = u.x | (s << 24);
             r.y = u.y | ((s & 0xff00u) << 16);
             r.z = u.z | ((s & 0xff0000u) << 8);
@@ -82,15 +100,17 @@ struct GrayGroup {
     }
 };
 
-// Register-staged prefetch of one tile plane (TilePrefetch's gray form): issue() starts the
-// HBM loads of source rows [ty0 + src_row0 - R, +ROWS) x columns [tx0 - L, tx0 + TW + L),
-// rows clamped to [row_lo, row_hi), columns to [0, width); commit() writes the plane words.
-template <int R, int ROWS, int NT, int P, int GUIDE>
-struct GrayPrefetch {
+// Register-staged prefetch of one tile's plane or planes (TilePrefetch's one-channel form), in
+// GROUPs of 4 pixels (GrayGroup: one plane; vip_joint_f32.hip's F32Group: a guide and a float
+// plane): issue() starts the HBM loads of source rows [ty0 + src_row0 - R, +ROWS) x columns
+// [tx0 - L, tx0 + TW + L), rows clamped to [row_lo, row_hi), columns to [0, width); commit()
+// writes the plane words: the GROUP's words() and, with GROUP::TWO, its source_words() to fplane.
+template <int R, int ROWS, int NT, int P, class GROUP>
+struct C1Prefetch {
     using G = Geom<R, P, 16>;
     static constexpr int NG = ROWS * G::GROUPS;
     static constexpr int K = (NG + NT - 1) / NT;
-    GrayGroup<GUIDE> raw[K];
+    GROUP raw[K];
 
     __device__ __forceinline__ void issue(const StencilArgs& a, int tx0, int ty0) {
 #pragma unroll
@@ -103,7 +123,7 @@ struct GrayPrefetch {
             raw[k].load(a.src, a.src_pitch, a.guide, a.guide_pitch, sy, tx0 - G::L + 4 * gc, a.width, a.aligned);
         }
     }
-    __device__ __forceinline__ void commit(uint32_t* plane) const {
+    __device__ __forceinline__ void commit(uint32_t* plane, uint32_t* fplane = nullptr) const {
 #pragma unroll
         for (int k = 0; k < K; ++k) {
             const int g = (int)threadIdx.x + k * NT;
@@ -111,6 +131,7 @@ struct GrayPrefetch {
             const int r = g / G::GROUPS;
             const int gc = g - r * G::GROUPS;
             *reinterpret_cast<uint4*>(plane + r * G::S + 4 * gc) = raw[k].words();
+            if constexpr (GROUP::TWO) *reinterpret_cast<uint4*>(fplane + r * G::S + 4 * gc) = raw[k].source_words();
         }
     }
 };
@@ -140,7 +161,9 @@ __device__ __forceinline__ void store_gray(const A& a, int oy, int x, const uint
 
 // ---- a tap's colour-LUT index d, in two forms. Each is a plane-word reading (guide(w): what
 // the index is formed from; source(w): the neighbour's float) plus index(g, nf, i): d of the
-// neighbour with guide word g and float nf against the thread's output i.
+// neighbour with guide word g and float nf against the thread's output i. TWO: the source has
+// a plane of its own and source() reads that plane's word; LUT_SHIFT: the LUT's byte address is
+// d << LUT_SHIFT | 4 * copy. (A third form, F32Sad, is vip_joint_f32.hip's.)
 constexpr int kGrayAdaEntries = 512;  // the adaptive form's int(dist) <= 510
 
 // bilateral / joint bilateral: the sum of absolute byte differences of the guide words
@@ -155,6 +178,8 @@ struct GraySad : GrayWord<GUIDE> {
 template <int P>
 struct GrayAdaptiveDist {
     static constexpr int ENTRIES = kGrayAdaEntries;
+    static constexpr bool TWO = false;
+    static constexpr int LUT_SHIFT = 7;
     float cf[P], of[P];
     __device__ __forceinline__ static uint32_t guide(uint32_t w) { return w; }
     __device__ __forceinline__ static float source(uint32_t w) { return (float)w; }
@@ -165,32 +190,32 @@ struct GrayAdaptiveDist {
 };
 
 // The tap loop of one tile row (row_taps' one-accumulator form): neighbour column j serves
-// output i at kx = j - L - i; per output the taps run in ascending kx.
+// output i at kx = j - L - i; per output the taps run in ascending kx. fplane: the source's
+// plane when DIST::TWO, else not read (the callers pass plane again).
 template <int HW, int L, int C0, int NC, bool FMA, int P, class DIST>
-__device__ __forceinline__ void gray_row_taps(const uint32_t* plane, int row_off, const float (&wsv)[HW + 1],
-                                              const char* lut, uint32_t lane4, const DIST& dist, float (&s)[P],
-                                              float (&sk)[P]) {
+__device__ __forceinline__ void gray_row_taps(const uint32_t* plane, const uint32_t* fplane, int row_off,
+                                              const float (&wsv)[HW + 1], const char* lut, uint32_t lane4,
+                                              const DIST& dist, float (&s)[P], float (&sk)[P]) {
     constexpr int D = kPipeDepth, NB = D + 1;
     constexpr int J0 = L - HW, J1 = L + P - 1 + HW;
     constexpr int LA = D + kRowLookahead;
     static_assert(J0 >= 4 * C0 && J1 < 4 * (C0 + NC), "row chunk range");
     auto chunk = [](int j) constexpr { return (j - 4 * C0) >> 2; };
     constexpr int PRE = chunk(J0 + LA < J1 ? J0 + LA : J1);
-    RowStream<C0, NC, false> row(plane, plane, row_off);
+    RowStream<C0, NC, DIST::TWO> row(plane, fplane, row_off);
 #pragma unroll
     for (int q = 0; q <= PRE; ++q) row.load(q);
     float wc[NB][P], nf[NB];
     auto issue = [&](int j) {
-        const uint32_t w = row.guide(j - 4 * C0);
-        const uint32_t g = DIST::guide(w);
+        const uint32_t g = DIST::guide(row.guide(j - 4 * C0));
         const int b = (j - J0) % NB;
-        nf[b] = DIST::source(w);
+        nf[b] = DIST::source(row.source(j - 4 * C0));
 #pragma unroll
         for (int i = 0; i < P; ++i) {
             const int kx = j - L - i;
             if (kx < -HW || kx > HW) continue;
             const uint32_t d = dist.index(g, nf[b], i);
-            wc[b][i] = *reinterpret_cast<const float*>(lut + ((d << 7) | lane4));
+            wc[b][i] = *reinterpret_cast<const float*>(lut + ((d << DIST::LUT_SHIFT) | lane4));
         }
     };
 #pragma unroll
@@ -213,6 +238,28 @@ __device__ __forceinline__ void gray_row_taps(const uint32_t* plane, int row_off
         }
         __builtin_amdgcn_sched_barrier(0);
     }
+}
+
+// Tile row ky of the persistent one-plane kernels, what for_each_row<R, true> runs per row: the
+// wave's priority band, the row's spatial weights (uniform: scalar loads), the taps, and the
+// accumulators pinned at the row's end (fence_accumulators). row_off: the plane word of the
+// thread's row ky, column tx * P. (joint_f32_kernel keeps a row body of its own: through this
+// function its 12-wave instantiations allocate registers differently.)
+template <int R, int HW, int L, bool FMA, int P, class DIST>
+__device__ __forceinline__ void gray_tile_row(const StencilArgs& a, int ky, const uint32_t* plane, int row_off,
+                                              const char* lut, uint32_t lane4, const DIST& dist, float (&s)[P],
+                                              float (&sk)[P]) {
+    const int aky = ky < 0 ? -ky : ky;
+    set_progress_priority((ky + R) * 4 / (2 * R + 1));
+    const float* const ws = a.ws + aky * kWsStride;
+    constexpr int C0 = (L - HW) / 4, C1 = (L + P - 1 + HW) / 4;
+    constexpr int NC = C1 - C0 + 1;
+    float wsv[HW + 1];
+#pragma unroll
+    for (int k = 0; k <= HW; ++k) wsv[k] = ws[k];
+    gray_row_taps<HW, L, C0, NC, FMA, P>(plane, plane, row_off, wsv, lut, lane4, dist, s, sk);
+#pragma unroll
+    for (int i = 0; i < P; ++i) __asm__ volatile("" : "+v"(s[i]), "+v"(sk[i]));
 }
 
 }  // namespace vip

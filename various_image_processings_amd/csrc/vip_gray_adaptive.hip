@@ -70,7 +70,6 @@ __global__ __launch_bounds__(kGrayAdaWaves * 64) void gray_adaptive_kernel(const
     constexpr int ROWS = TH + 2 * R;
     constexpr int K = 2 * R + 1;
     constexpr int VW = G::GROUPS * 4;  // plane words in use per row (TW + 2L)
-    static_assert(kGrayCopies == 32, "LUT address: d << 7");
     static_assert(gray_adaptive_vbox<R>(), "LUT + plane + vertical sums do not fit LDS");
     static_assert(TH % 4 == 0 && VW % 8 == 0, "vertical-sum runs of 4 rows; 16-byte aligned u16 rows");
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
@@ -88,7 +87,7 @@ __global__ __launch_bounds__(kGrayAdaWaves * 64) void gray_adaptive_kernel(const
 
     // persistent: workgroup b filters tiles b, b + grid, ... (xcd_tile's placement)
     int tile = blockIdx.x;
-    GrayPrefetch<R, ROWS, NT, P, 0> pf;
+    C1Prefetch<R, ROWS, NT, P, GrayGroup<0>> pf;
     LutStage<NT, kGrayAdaEntries, kGrayCopies> ls;
     ls.load(a.color);
     {
@@ -163,20 +162,8 @@ __global__ __launch_bounds__(kGrayAdaWaves * 64) void gray_adaptive_kernel(const
             for (int i = 0; i < P; ++i) s[i] = sk[i] = 0.f;
 
             for_each_row<R, true>([&](const int ky, auto hwc) {
-                constexpr int HW = decltype(hwc)::value;
-                const int aky = ky < 0 ? -ky : ky;
-                set_progress_priority((ky + R) * 4 / (2 * R + 1));
                 const int row_off = (ty + R + ky) * G::S + tx * P;
-                const float* const ws = a.ws + aky * kWsStride;
-                constexpr int C0 = (G::L - HW) / 4, C1 = (G::L + P - 1 + HW) / 4;
-                constexpr int NC = C1 - C0 + 1;
-                float wsv[HW + 1];
-#pragma unroll
-                for (int k = 0; k <= HW; ++k) wsv[k] = ws[k];
-                gray_row_taps<HW, G::L, C0, NC, FMA, P>(plane, row_off, wsv, lut_bytes, lane4, dist, s, sk);
-                // pin the accumulators at the row's end (fence_accumulators)
-#pragma unroll
-                for (int i = 0; i < P; ++i) __asm__ volatile("" : "+v"(s[i]), "+v"(sk[i]));
+                gray_tile_row<R, decltype(hwc)::value, G::L, FMA>(a, ky, plane, row_off, lut_bytes, lane4, dist, s, sk);
             });
 
             uint32_t o[P];
@@ -192,25 +179,13 @@ __global__ __launch_bounds__(kGrayAdaWaves * 64) void gray_adaptive_kernel(const
     }
 }
 
-template <int R, bool FMA>
-static int launch_gray_adaptive_r(const StencilArgs& a, hipStream_t stream) {
-    using G = Geom<R, kGrayAdaP, 16>;
-    constexpr int LDS = gray_adaptive_lds_bytes<R>();
-    static_assert(LDS <= kLdsBudget, "tile does not fit LDS");
-    constexpr auto kern = gray_adaptive_kernel<R, FMA>;
-    return launch_persistent<kern, nullptr, LDS, kGrayAdaWaves, G::TW, kGrayAdaWaves * G::RPW, false>(a, false, stream);
-}
-
 template <bool FMA>
 static int launch_gray_adaptive_dispatch(int radius, const StencilArgs& a, hipStream_t stream) {
-    switch (radius) {
-#define VIP_CASE(RR) \
-    case RR: return launch_gray_adaptive_r<RR, FMA>(a, stream);
-        VIP_CASE(1) VIP_CASE(2) VIP_CASE(3) VIP_CASE(4) VIP_CASE(5) VIP_CASE(6) VIP_CASE(7) VIP_CASE(8)
-        VIP_CASE(9) VIP_CASE(10) VIP_CASE(11) VIP_CASE(12) VIP_CASE(13) VIP_CASE(14) VIP_CASE(15)
-#undef VIP_CASE
-        default: return VIP_ERR_UNSUPPORTED_KSIZE;
-    }
+    return dispatch_radius(radius, [&](auto rc) {
+        constexpr int R = decltype(rc)::value;
+        return launch_c1_tiles<gray_adaptive_kernel<R, FMA>, gray_adaptive_lds_bytes<R>(), kGrayAdaWaves,
+                               Geom<R, kGrayAdaP, 16>>(a, stream);
+    });
 }
 
 int launch_gray_adaptive(int radius, bool fma, const StencilArgs& a, hipStream_t s) {

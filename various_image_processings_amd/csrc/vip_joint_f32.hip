@@ -13,7 +13,9 @@
 // <..., JOINT>), not one 64-bit plane: a ds_read_b128 of either plane then feeds 4 neighbours
 // exactly as the gray kernels' one plane does, the row strides and their bank-conflict-free
 // ds_read_b128 groups (Geom::S, rt_stride) carry over unchanged, and RowStream<.., TWO> already
-// reads such a pair. A 64-bit plane would interleave guide and float in every ds_read_b128
+// reads such a pair: the guide loader, the tile prefetch and the tap loop of a tile row are the
+// gray kernels' (vip_gray.hpp: Guide4, C1Prefetch on F32Group, gray_row_taps with the F32Sad
+// index). A 64-bit plane would interleave guide and float in every ds_read_b128
 // (2 neighbours per read) and double every row stride. The guide plane holds the bare guide
 // word (G, or B | G << 8 | R << 16), so v_sad_u8 needs no mask; the float plane is the
 // neighbour itself: a tap is the gray kernels' minus the byte -> float conversion per
@@ -56,7 +58,7 @@ struct F32Guide {
     static_assert(GUIDE == 1 || GUIDE == 3, "guide channels");
     static constexpr int ENTRIES = GUIDE == 3 ? 768 : 256;  // colour-LUT entries d can reach
     static constexpr int COPIES = GUIDE == 3 ? 16 : 32;     // interleaved copies of each entry
-    static constexpr int SHIFT = COPIES == 32 ? 7 : 6;      // LUT byte address: d << SHIFT | 4 * copy
+    static constexpr int LUT_SHIFT = COPIES == 32 ? 7 : 6;  // LUT byte address: d << LUT_SHIFT | 4 * copy
     static constexpr int LUTW = ENTRIES * COPIES;
 };
 // Waves per workgroup: the most whose planes fit LDS (pick_waves), and 12 from the radius on at
@@ -72,10 +74,12 @@ constexpr int f32_waves() {
 }
 
 // 4 pixels of one image row from column x (columns clamped to the image): the guide's 1 or 3
-// dwords and the source's 4 floats, as loaded from HBM, and as the plane words they become.
+// dwords and the source's 4 floats, as loaded from HBM, and as the plane words they become
+// (words(): the guide plane's; source_words(): the float plane's).
 template <int GUIDE>
 struct F32Group {
-    uint32_t g0, g1, g2;
+    static constexpr bool TWO = true;
+    Guide4<GUIDE> g;
     float4 f;
 
     __device__ __forceinline__ void load(const uint8_t* src, long long src_pitch, const uint8_t* guide,
@@ -90,63 +94,18 @@ struct F32Group {
             f.z = frow[clampi(x + 2, 0, width - 1)];
             f.w = frow[clampi(x + 3, 0, width - 1)];
         }
-        const uint8_t* row = guide + (long long)sy * guide_pitch;
-        g0 = g1 = g2 = 0u;
-        if constexpr (GUIDE == 1) {
-            g0 = load_gray4(row, x, width, aligned & kF32GuideWords);
-        } else if ((aligned & kF32GuideWords) && interior) {
-            const uint32_t* w = reinterpret_cast<const uint32_t*>(row + 3 * x);
-            g0 = w[0];
-            g1 = w[1];
-            g2 = w[2];
-        } else {
-            const uint32_t q0 = load_rgb(row, clampi(x + 0, 0, width - 1));
-            const uint32_t q1 = load_rgb(row, clampi(x + 1, 0, width - 1));
-            const uint32_t q2 = load_rgb(row, clampi(x + 2, 0, width - 1));
-            const uint32_t q3 = load_rgb(row, clampi(x + 3, 0, width - 1));
-            g0 = q0 | (q1 << 24);
-            g1 = (q1 >> 8) | (q2 << 16);
-            g2 = (q2 >> 16) | (q3 << 8);
-        }
+        // with or without `interior` the flag means the same (Guide4 tests the columns itself); each
+        // guide form gets the spelling that compiles to the code it had (profiles/c1_shared_isa.txt)
+        const int gwords = aligned & kF32GuideWords;
+        g.load(guide + (long long)sy * guide_pitch, x, width, GUIDE == 3 ? (gwords && interior) : gwords);
     }
-    __device__ __forceinline__ uint4 guide_words() const {
-        if constexpr (GUIDE == 1) return make_uint4(g0 & 0xffu, (g0 >> 8) & 0xffu, (g0 >> 16) & 0xffu, g0 >> 24);
-        return unpack_rgb4(g0, g1, g2);
+    __device__ __forceinline__ uint4 words() const {
+        if constexpr (GUIDE == 1)
+            return make_uint4(g.g0 & 0xffu, (g.g0 >> 8) & 0xffu, (g.g0 >> 16) & 0xffu, g.g0 >> 24);
+        return unpack_rgb4(g.g0, g.g1, g.g2);
     }
     __device__ __forceinline__ uint4 source_words() const {
         return make_uint4(__float_as_uint(f.x), __float_as_uint(f.y), __float_as_uint(f.z), __float_as_uint(f.w));
-    }
-};
-
-// Register-staged prefetch of one tile's two planes (GrayPrefetch's two-plane form)
-template <int R, int ROWS, int NT, int GUIDE>
-struct F32Prefetch {
-    using G = Geom<R, kF32P, 16>;
-    static constexpr int NG = ROWS * G::GROUPS;
-    static constexpr int K = (NG + NT - 1) / NT;
-    F32Group<GUIDE> raw[K];
-
-    __device__ __forceinline__ void issue(const StencilArgs& a, int tx0, int ty0) {
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-            const int g = (int)threadIdx.x + k * NT;
-            if (NG % NT != 0 && k == K - 1 && g >= NG) continue;
-            const int r = g / G::GROUPS;
-            const int gc = g - r * G::GROUPS;
-            const int sy = clampi(ty0 + a.src_row0 - R + r, a.row_lo, a.row_hi - 1);
-            raw[k].load(a.src, a.src_pitch, a.guide, a.guide_pitch, sy, tx0 - G::L + 4 * gc, a.width, a.aligned);
-        }
-    }
-    __device__ __forceinline__ void commit(uint32_t* gplane, uint32_t* fplane) const {
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-            const int g = (int)threadIdx.x + k * NT;
-            if (NG % NT != 0 && k == K - 1 && g >= NG) continue;
-            const int r = g / G::GROUPS;
-            const int gc = g - r * G::GROUPS;
-            *reinterpret_cast<uint4*>(gplane + r * G::S + 4 * gc) = raw[k].guide_words();
-            *reinterpret_cast<uint4*>(fplane + r * G::S + 4 * gc) = raw[k].source_words();
-        }
     }
 };
 
@@ -169,56 +128,18 @@ __device__ __forceinline__ void store_f32(const A& a, int oy, int x, const float
         if (x + i < a.width) p[i] = o[i];
 }
 
-// The tap loop of one tile row (gray_row_taps' two-plane form): neighbour column j serves
-// output i at kx = j - L - i; per output the taps run in ascending kx. The neighbour's float is
-// its float-plane word as it stands.
-template <int HW, int L, int C0, int NC, bool FMA, int P, int SHIFT>
-__device__ __forceinline__ void f32_row_taps(const uint32_t* gplane, const uint32_t* fplane, int row_off,
-                                             const float (&wsv)[HW + 1], const char* lut, uint32_t lanec,
-                                             const uint32_t (&ctr)[P], float (&s)[P], float (&sk)[P]) {
-    constexpr int D = kPipeDepth, NB = D + 1;
-    constexpr int J0 = L - HW, J1 = L + P - 1 + HW;
-    constexpr int LA = D + kRowLookahead;
-    static_assert(J0 >= 4 * C0 && J1 < 4 * (C0 + NC), "row chunk range");
-    auto chunk = [](int j) constexpr { return (j - 4 * C0) >> 2; };
-    constexpr int PRE = chunk(J0 + LA < J1 ? J0 + LA : J1);
-    RowStream<C0, NC, true> row(gplane, fplane, row_off);
-#pragma unroll
-    for (int q = 0; q <= PRE; ++q) row.load(q);
-    float wc[NB][P], nf[NB];
-    auto issue = [&](int j) {
-        const uint32_t g = row.guide(j - 4 * C0);
-        const int b = (j - J0) % NB;
-        nf[b] = __uint_as_float(row.source(j - 4 * C0));
-#pragma unroll
-        for (int i = 0; i < P; ++i) {
-            const int kx = j - L - i;
-            if (kx < -HW || kx > HW) continue;
-            const uint32_t d = __builtin_amdgcn_sad_u8(g, ctr[i], 0u);
-            wc[b][i] = *reinterpret_cast<const float*>(lut + ((d << SHIFT) | lanec));
-        }
-    };
-#pragma unroll
-    for (int j = J0; j < J0 + D && j <= J1; ++j) issue(j);
-#pragma unroll
-    for (int j = J0; j <= J1; ++j) {
-        if (j + LA <= J1 && ((j + LA) & 3) == 0 && chunk(j + LA) > PRE) row.load(chunk(j + LA));
-        if (j + D <= J1) issue(j + D);
-        const int b = (j - J0) % NB;
-#pragma unroll
-        for (int i = 0; i < P; ++i) {
-            const int kx = j - L - i;
-            if (kx < -HW || kx > HW) continue;
-            const float w = wc[b][i] * wsv[kx < 0 ? -kx : kx];
-            if constexpr (FMA)
-                s[i] = __builtin_fmaf(nf[b], w, s[i]);
-            else
-                s[i] = s[i] + nf[b] * w;
-            sk[i] = sk[i] + w;
-        }
-        __builtin_amdgcn_sched_barrier(0);
+// A tap's colour-LUT index (as vip_gray.hpp's GraySad): the guide plane's word is the bare
+// guide, the float plane's word the neighbour's float as it stands.
+template <int GUIDE, int P>
+struct F32Sad : F32Guide<GUIDE> {
+    static constexpr bool TWO = true;
+    uint32_t ctr[P];  // the outputs' centre guide words
+    __device__ __forceinline__ static uint32_t guide(uint32_t w) { return w; }
+    __device__ __forceinline__ static float source(uint32_t w) { return __uint_as_float(w); }
+    __device__ __forceinline__ uint32_t index(uint32_t g, float, int i) const {
+        return __builtin_amdgcn_sad_u8(g, ctr[i], 0u);
     }
-}
+};
 
 template <int R, int GUIDE, bool FMA>
 __global__ __launch_bounds__((f32_waves<R, GUIDE>() * 64)) void joint_f32_kernel(const StencilArgs a) {
@@ -244,7 +165,7 @@ __global__ __launch_bounds__((f32_waves<R, GUIDE>() * 64)) void joint_f32_kernel
 
     // persistent: workgroup b filters tiles b, b + grid, ... (xcd_tile's placement)
     int tile = blockIdx.x;
-    F32Prefetch<R, ROWS, NT, GUIDE> pf;
+    C1Prefetch<R, ROWS, NT, P, F32Group<GUIDE>> pf;
     LutStage<NT, W::ENTRIES, W::COPIES> ls;
     ls.load(a.color);
     {
@@ -264,16 +185,16 @@ __global__ __launch_bounds__((f32_waves<R, GUIDE>() * 64)) void joint_f32_kernel
             pf.issue(a, (n % a.tiles_x) * G::TW, (n / a.tiles_x) * TH);
         }
         if (ty0 + wave * G::RPW < a.out_rows) {  // wave-uniform: skip rows past the band
-            uint32_t ctr[P];  // the outputs' centre guide words
+            F32Sad<GUIDE, P> dist;
             {
                 const uint4* c = reinterpret_cast<const uint4*>(gplane + (ty + R) * G::S + tx * P + G::L);
 #pragma unroll
                 for (int q = 0; q < P / 4; ++q) {
                     const uint4 v = c[q];
-                    ctr[4 * q + 0] = v.x;
-                    ctr[4 * q + 1] = v.y;
-                    ctr[4 * q + 2] = v.z;
-                    ctr[4 * q + 3] = v.w;
+                    dist.ctr[4 * q + 0] = v.x;
+                    dist.ctr[4 * q + 1] = v.y;
+                    dist.ctr[4 * q + 2] = v.z;
+                    dist.ctr[4 * q + 3] = v.w;
                 }
             }
             float s[P], sk[P];
@@ -281,21 +202,20 @@ __global__ __launch_bounds__((f32_waves<R, GUIDE>() * 64)) void joint_f32_kernel
             for (int i = 0; i < P; ++i) s[i] = sk[i] = 0.f;
 
             for_each_row<R, true>([&](const int ky, auto hwc) {
-                constexpr int HW = decltype(hwc)::value;
-                const int aky = ky < 0 ? -ky : ky;
-                set_progress_priority((ky + R) * 4 / (2 * R + 1));
                 // 4 * (the thread's uint4 index + the row's constant): RowStream's row_off >> 2 then
                 // folds, and every row of a plane is one base register plus a ds_read immediate
                 // (as (ty + R + ky) * S + tx * P the 2 x (2R + 1) row addresses each take a VGPR)
                 const int row_off = 4 * (base4 + (R + ky) * (G::S / 4));
+                constexpr int HW = decltype(hwc)::value;
+                const int aky = ky < 0 ? -ky : ky;
+                set_progress_priority((ky + R) * 4 / (2 * R + 1));
                 const float* const ws = a.ws + aky * kWsStride;
                 constexpr int C0 = (G::L - HW) / 4, C1 = (G::L + P - 1 + HW) / 4;
                 constexpr int NC = C1 - C0 + 1;
                 float wsv[HW + 1];
 #pragma unroll
                 for (int k = 0; k <= HW; ++k) wsv[k] = ws[k];
-                f32_row_taps<HW, G::L, C0, NC, FMA, P, W::SHIFT>(gplane, fplane, row_off, wsv, lut_bytes, lanec, ctr, s,
-                                                                 sk);
+                gray_row_taps<HW, G::L, C0, NC, FMA, P>(gplane, fplane, row_off, wsv, lut_bytes, lanec, dist, s, sk);
                 // pin the accumulators at the row's end (fence_accumulators)
 #pragma unroll
                 for (int i = 0; i < P; ++i) __asm__ volatile("" : "+v"(s[i]), "+v"(sk[i]));
@@ -314,26 +234,14 @@ __global__ __launch_bounds__((f32_waves<R, GUIDE>() * 64)) void joint_f32_kernel
     }
 }
 
-template <int R, int GUIDE, bool FMA>
-static int launch_joint_f32_r(const StencilArgs& a, hipStream_t stream) {
-    using G = Geom<R, kF32P, 16>;
-    constexpr int WAVES = f32_waves<R, GUIDE>();
-    constexpr int LDS = lds_bytes<R, WAVES, 2, F32Guide<GUIDE>::LUTW, kF32P, 16>();
-    static_assert(WAVES >= 12 && LDS <= kLdsBudget, "tile does not fit LDS");
-    constexpr auto kern = joint_f32_kernel<R, GUIDE, FMA>;
-    return launch_persistent<kern, nullptr, LDS, WAVES, G::TW, WAVES * G::RPW, false>(a, false, stream);
-}
-
 template <int GUIDE, bool FMA>
 static int launch_joint_f32_dispatch(int radius, const StencilArgs& a, hipStream_t stream) {
-    switch (radius) {
-#define VIP_CASE(RR) \
-    case RR: return launch_joint_f32_r<RR, GUIDE, FMA>(a, stream);
-        VIP_CASE(1) VIP_CASE(2) VIP_CASE(3) VIP_CASE(4) VIP_CASE(5) VIP_CASE(6) VIP_CASE(7) VIP_CASE(8)
-        VIP_CASE(9) VIP_CASE(10) VIP_CASE(11) VIP_CASE(12) VIP_CASE(13) VIP_CASE(14) VIP_CASE(15)
-#undef VIP_CASE
-        default: return VIP_ERR_UNSUPPORTED_KSIZE;
-    }
+    return dispatch_radius(radius, [&](auto rc) {
+        constexpr int R = decltype(rc)::value, WAVES = f32_waves<R, GUIDE>();
+        constexpr int LDS = lds_bytes<R, WAVES, 2, F32Guide<GUIDE>::LUTW, kF32P, 16>();
+        static_assert(WAVES >= 12, "tile does not fit LDS");
+        return launch_c1_tiles<joint_f32_kernel<R, GUIDE, FMA>, LDS, WAVES, Geom<R, kF32P, 16>>(a, stream);
+    });
 }
 
 int launch_joint_f32(int radius, int guide_channels, bool fma, const StencilArgs& a, hipStream_t s) {
@@ -410,7 +318,7 @@ __global__ __launch_bounds__(kRtWaves * 64) void joint_f32_rt_kernel(const RtArg
                 const int sy = clampi(ty0 + a.src_row0 - R + r, a.row_lo, a.row_hi - 1);
                 F32Group<GUIDE> grp;
                 grp.load(a.src, a.src_pitch, a.guide, a.guide_pitch, sy, tx0 - L + 4 * gc, a.width, a.aligned);
-                gw = grp.guide_words();
+                gw = grp.words();
                 fw = grp.source_words();
             }
             *reinterpret_cast<uint4*>(gplane + r * S + 4 * gc) = gw;
@@ -447,7 +355,7 @@ __global__ __launch_bounds__(kRtWaves * 64) void joint_f32_rt_kernel(const RtArg
             for (int i = 0; i < P; ++i) {
                 const int j = t + i;
                 const uint32_t d = __builtin_amdgcn_sad_u8(j < 4 ? cur.g[j & 3] : nxt.g[j & 3], ctr[i], 0u);
-                wc[t][i] = *reinterpret_cast<const float*>(lut_bytes + ((d << W::SHIFT) | lanec));
+                wc[t][i] = *reinterpret_cast<const float*>(lut_bytes + ((d << W::LUT_SHIFT) | lanec));
             }
 #pragma unroll
         for (int t = 0; t < 4; ++t)

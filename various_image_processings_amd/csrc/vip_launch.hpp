@@ -6,6 +6,7 @@
 
 #include <atomic>
 #include <type_traits>
+#include <utility>
 
 #include <hip/hip_ext.h>
 
@@ -261,6 +262,25 @@ static int launch_persistent(const StencilArgs& a, bool cut_tail, hipStream_t st
     if (multi && cut_tail) plan_tail(args, blocks, WAVES);
     launch(kern, dim3(blocks), dim3(WAVES * 64), LDS, stream, args);
     return (int)hipGetLastError();
+}
+
+// The one-channel kernels' persistent launch: one frame, whole tiles of G::TW x WAVES * G::RPW
+// pixels (G: the kernel's Geom), no absolute LDS address.
+template <auto KERN, int LDS, int WAVES, class G>
+static int launch_c1_tiles(const StencilArgs& a, hipStream_t stream) {
+    static_assert(LDS <= kLdsBudget, "tile does not fit LDS");
+    return launch_persistent<KERN, nullptr, LDS, WAVES, G::TW, WAVES * G::RPW, false>(a, false, stream);
+}
+
+// A run-time radius as a compile-time one: f(std::integral_constant<int, R>) for radius R in
+// 1..kMaxRadius (every R is instantiated, in ascending order), VIP_ERR_UNSUPPORTED_KSIZE otherwise.
+template <class F>
+static int dispatch_radius(int radius, F&& f) {
+    int rc = VIP_ERR_UNSUPPORTED_KSIZE;
+    [&]<int... I>(std::integer_sequence<int, I...>) {
+        (void)(... || (radius == I + 1 && (rc = f(std::integral_constant<int, I + 1>{}), true)));
+    }(std::make_integer_sequence<int, kMaxRadius>{});
+    return rc;
 }
 
 }  // namespace vip
