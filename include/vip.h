@@ -39,6 +39,7 @@ extern "C" {
 typedef struct vip_bilateral_s* vip_bilateral_t;
 typedef struct vip_adaptive_s* vip_adaptive_t;
 typedef struct vip_texture_s* vip_texture_t;
+typedef struct vip_upsample_s* vip_upsample_t;
 
 int vip_abi_version(void);
 /* The kernels the calling thread launched through this library since its previous call,
@@ -70,11 +71,13 @@ int vip_max_radius(void);
  * so: bilateral 65, joint bilateral 47, adaptive 63, texture 24 (its JBF is 2k-1 <= 47).
  * Bilateral, joint and adaptive take odd ksize from 1 (radius 0: output = input for
  * sigma_space > 0); the texture filter any ksize from 1. The C++ and Python layers take
- * the same sets. Returns VIP_ERR_INVALID_ARGUMENT for an unknown filter. */
+ * the same sets. Joint bilateral upsampling (no reference counterpart) takes odd ksize 1..9,
+ * in low-resolution pixels. Returns VIP_ERR_INVALID_ARGUMENT for an unknown filter. */
 #define VIP_FILTER_BILATERAL 0
 #define VIP_FILTER_JOINT 1
 #define VIP_FILTER_ADAPTIVE 2
 #define VIP_FILTER_TEXTURE 3
+#define VIP_FILTER_UPSAMPLE 4
 int vip_max_ksize(int filter);
 
 /* Kernel selection, process-wide (no reference counterpart; results are identical either
@@ -225,6 +228,55 @@ int vip_joint_bilateral_run_rows_f32(vip_bilateral_t h, const float* d_src, size
                                      const uint8_t* d_guide, size_t guide_pitch, int guide_channels, float* d_dst,
                                      size_t dst_pitch, int out_rows, int src_row0, int row_lo, int row_hi,
                                      void* stream);
+/* ---- joint bilateral upsampling (Kopf et al. 2007; no counterpart in the reference's API): a
+ * field f solved at 1/2, 1/4 or 1/8 scale is brought up to the frame under the full-resolution
+ * image, in one launch, with no full-resolution float intermediate.
+ * Inputs and sizes: W x H is the output size, the full-resolution guide's. The scale s is 2, 4 or
+ * 8. The low-resolution size is w = ceil(W / s), h = ceil(H / s) (vip_upsample_low_size). f is
+ * w x h float32 with finite values. g is the w x h low-resolution guide, u8 with 1 or 3
+ * interleaved channels; the caller supplies it: it is the image the field was solved on, whether
+ * a subsample or an area average; the library does not derive it. G is the W x H full-resolution
+ * guide with the same channel count. R = ksize / 2, ksize odd, 1..9, in low-resolution pixels.
+ * Per output pixel (x, y): cx = x / s, px = x % s, cy = y / s, py = y % s, in integer
+ * arithmetic. The taps run in row-major order over ky, kx in [-R, R]: the whole square, no disc.
+ *   ix   = clamp(cx + kx, 0, w - 1),  iy = clamp(cy + ky, 0, h - 1)
+ *   ox   = 2 s kx + (s - 1) - 2 px,   oy likewise
+ *          (the offset from the output pixel to the centre of low-resolution cell cx + kx, in
+ *          half full-resolution pixels: integers, symmetric in the phase)
+ *   wsp  = space_weight(ox^2 + oy^2, 2 s sigma_space)
+ *          (the function every handle's spatial LUT is built with: exp(-r2 / (2 sigma^2)), float
+ *          or double coefficient by profile; 2 s sigma_space is an exact float product, so
+ *          sigma_space is in low-resolution pixels)
+ *   d    = |g(ix,iy) - G(x,y)|      (guide_channels 1)
+ *        = |dB| + |dG| + |dR|       (guide_channels 3; the 768-entry colour LUT wc of sigma_color)
+ *   wgt  = wsp * wc[d]              (one binary32 product)
+ *   s    = fmaf(f(ix,iy), wgt, s)   VIP_NUMERICS_CUDA
+ *   s    = s + f(ix,iy) * wgt       VIP_NUMERICS_CPP
+ *   sumk = sumk + wgt
+ *   dst(x,y) = sumk == 0 ? f(cx, cy) : s / sumk
+ * Arithmetic is binary32 with gradual underflow (the kernels run in denormal mode 3 like their
+ * siblings). No tap has weight 1, so sumk may be subnormal: the division is IEEE. sumk may also
+ * be exactly zero, when every wc[d] has underflowed: then the nearest low-resolution sample is
+ * returned (cx <= w - 1 always, so no clamp is needed). An Inf or NaN in f gives unspecified
+ * values but can never fault: every address comes from coordinates and guides.
+ * The handle holds the colour LUT and the device table of spatial weights and is read-only
+ * after create: it may run on several streams at once. Each call is one launch
+ * (vip::upsample_f32_kernel<R, S, GUIDE, FMA>), asynchronous, with no device allocation; the
+ * launch log and vip_kernel_timing_* see it. Pitches are in bytes. d_src_lo and d_dst need base
+ * and pitch that are multiples of 4; 16-byte accesses are used only where base and pitch allow.
+ * The guides may have any base and pitch. No byte of d_dst is written at column >= width or
+ * row >= height. VIP_ERR_INVALID_ARGUMENT: a null handle or pointer, a non-positive size, a scale
+ * not in {2, 4, 8}, guide_channels not 1 or 3, a misaligned float pointer or pitch, a pitch
+ * smaller than a row; VIP_ERR_UNSUPPORTED_KSIZE: an even ksize or one above 9
+ * (vip_max_ksize(VIP_FILTER_UPSAMPLE)); VIP_ERR_ALIASING: d_dst equals any input.
+ * vip_set_stencil_path and the vip_bilateral_set_* knobs do not apply. */
+int vip_upsample_create(vip_upsample_t* out, int width, int height, int scale, int ksize, float sigma_space,
+                        float sigma_color, int numerics);
+int vip_upsample_destroy(vip_upsample_t h);
+int vip_upsample_low_size(int width, int height, int scale, int* low_width, int* low_height);
+int vip_upsample_run_f32(vip_upsample_t h, const float* d_src_lo, size_t src_pitch, const uint8_t* d_guide_lo,
+                         size_t guide_lo_pitch, const uint8_t* d_guide, size_t guide_pitch, int guide_channels,
+                         float* d_dst, size_t dst_pitch, void* stream);
 /* Tuning knob, process-wide (no reference counterpart): waves per workgroup of the plain
  * bilateral kernel for radius <= 8. 0 (default) = chosen per launch from the frame's
  * tile count (small frames take 8 or 4 waves and smaller tiles so more CUs work);

@@ -11,6 +11,7 @@ from ._lib import (  # noqa: F401
     VIP_FILTER_BILATERAL,
     VIP_FILTER_JOINT,
     VIP_FILTER_TEXTURE,
+    VIP_FILTER_UPSAMPLE,
     VIP_PATH_AUTO,
     VIP_PATH_RUNTIME,
     VipError,
@@ -22,6 +23,7 @@ from .filters import (  # noqa: F401
     CudaAdaptiveBilateralFilter,
     CudaBilateralFilter,
     CudaBilateralTextureFilter,
+    CudaJointBilateralUpsample,
     DeviceImage,
     cuda_gradient,
     device_synchronize,

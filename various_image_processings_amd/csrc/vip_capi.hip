@@ -94,6 +94,8 @@ static void build_color(int len, float sigma_color, int numerics, float* out) {
 // Even ksizes stay rejected: the reference sizes its tile for ksize - 1 halo columns but
 // reads 2 * (ksize / 2), past the tile.
 constexpr int kMaxKsizeBilateral = 65, kMaxKsizeJoint = 47, kMaxKsizeAdaptive = 63, kMaxKsizeTexture = 24;
+// joint bilateral upsampling has no reference counterpart: its ksize counts low-resolution pixels
+constexpr int kMaxKsizeUpsample = 2 * kUpMaxRadius + 1;
 static bool valid_ksize(int ksize, int max_ksize) { return ksize >= 1 && (ksize & 1) && ksize <= max_ksize; }
 
 // vip_set_stencil_path: VIP_PATH_AUTO (templated kernels for radius 1..15, the
@@ -267,6 +269,14 @@ struct vip_bilateral_s : StencilHandle {
 };
 
 struct vip_adaptive_s : StencilHandle {};
+
+// Joint bilateral upsampling: the frame, the scale and the two device tables. Read-only after
+// create, so one handle serves any number of streams.
+struct vip_upsample_s {
+    int width, height, scale, radius, numerics, low_width, low_height;
+    float* d_color;  // 768-entry colour LUT
+    float* d_wsp;    // spatial weights (upload_upsample_space)
+};
 
 // Folded joint-kernel tables: table t (the t-th distinct r^2 of the disc, ascending)
 // entry d = RN(ws(r^2) * wc[d]) for d < kFoldEntries -- the product the kernel's unfolded
@@ -473,6 +483,7 @@ int vip_max_ksize(int filter) {
         case VIP_FILTER_JOINT: return kMaxKsizeJoint;
         case VIP_FILTER_ADAPTIVE: return kMaxKsizeAdaptive;
         case VIP_FILTER_TEXTURE: return kMaxKsizeTexture;
+        case VIP_FILTER_UPSAMPLE: return kMaxKsizeUpsample;
         default: return VIP_ERR_INVALID_ARGUMENT;
     }
 }
@@ -506,7 +517,8 @@ const char* vip_error_string(int code) {
         case 0: return "success";
         case VIP_ERR_INVALID_ARGUMENT: return "invalid argument";
         case VIP_ERR_UNSUPPORTED_KSIZE:
-            return "unsupported ksize (odd, 1..65 bilateral, 1..47 joint bilateral, 1..63 adaptive; texture 1..24)";
+            return "unsupported ksize (odd, 1..65 bilateral, 1..47 joint bilateral, 1..63 adaptive, 1..9 upsampling; "
+                   "texture 1..24)";
         case VIP_ERR_ALIASING: return "source and destination alias";
         default: return hipGetErrorString((hipError_t)code);
     }
@@ -659,6 +671,101 @@ int vip_joint_bilateral_run_f32(vip_bilateral_t h, const float* d_src, size_t sr
     if (!h) return VIP_ERR_INVALID_ARGUMENT;
     return vip_joint_bilateral_run_rows_f32(h, d_src, src_pitch, d_guide, guide_pitch, guide_channels, d_dst,
                                             dst_pitch, h->height, 0, 0, h->height, stream);
+}
+
+// ---- joint bilateral upsampling (vip_upsample.hip): a handle of its own, since the spatial
+// table depends on the scale
+static bool valid_scale(int s) { return s == 2 || s == 4 || s == 8; }
+
+// The device table of spatial weights: [n][n], n = scale * radius + scale / 2; entry [ay][ax] is
+// the weight of the offset (2 ax + 1, 2 ay + 1) in half full-resolution pixels under
+// 2 * scale * sigma_space. Every tap of every phase reads one: its offset
+// 2 s k + (s - 1) - 2 p is odd with |.| <= 2 s R + s - 1 = 2 n - 1, and the weight is even in both.
+static int upload_upsample_space(vip_upsample_s* h, float sigma_space) {
+    const int n = h->scale * h->radius + h->scale / 2;
+    const float sigma = (float)(2 * h->scale) * sigma_space;  // exact: a power of two times a float
+    std::vector<float> host((size_t)n * n);
+    for (int ay = 0; ay < n; ++ay)
+        for (int ax = 0; ax < n; ++ax) {
+            const int ox = 2 * ax + 1, oy = 2 * ay + 1;
+            host[(size_t)ay * n + ax] = space_weight(ox * ox + oy * oy, sigma, h->numerics);
+        }
+    VIP_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&h->d_wsp), sizeof(float) * host.size()));
+    VIP_HIP_CHECK(hipMemcpy(h->d_wsp, host.data(), sizeof(float) * host.size(), hipMemcpyHostToDevice));
+    return 0;
+}
+
+int vip_upsample_low_size(int width, int height, int scale, int* low_width, int* low_height) {
+    if (width <= 0 || height <= 0 || !valid_scale(scale) || !low_width || !low_height) return VIP_ERR_INVALID_ARGUMENT;
+    *low_width = (width + scale - 1) / scale;
+    *low_height = (height + scale - 1) / scale;
+    return 0;
+}
+
+int vip_upsample_destroy(vip_upsample_t h) {
+    if (!h) return 0;
+    if (h->d_wsp) (void)hipFree(h->d_wsp);
+    const int rc = h->d_color ? (int)hipFree(h->d_color) : 0;
+    delete h;
+    return rc;
+}
+
+int vip_upsample_create(vip_upsample_t* out, int width, int height, int scale, int ksize, float sigma_space,
+                        float sigma_color, int numerics) {
+    if (!out || width <= 0 || height <= 0 || !valid_scale(scale)) return VIP_ERR_INVALID_ARGUMENT;
+    if (!valid_ksize(ksize, kMaxKsizeUpsample)) return VIP_ERR_UNSUPPORTED_KSIZE;
+    vip_upsample_s* h = new (std::nothrow) vip_upsample_s();
+    if (!h) return (int)hipErrorOutOfMemory;
+    h->width = width;
+    h->height = height;
+    h->scale = scale;
+    h->radius = ksize / 2;
+    h->numerics = numerics == VIP_NUMERICS_CPP ? VIP_NUMERICS_CPP : VIP_NUMERICS_CUDA;
+    (void)vip_upsample_low_size(width, height, scale, &h->low_width, &h->low_height);
+    int nonzero = 0;
+    int rc = upload_color(&h->d_color, 768, sigma_color, h->numerics, &nonzero);
+    if (!rc) rc = upload_upsample_space(h, sigma_space);
+    if (rc) {
+        vip_upsample_destroy(h);
+        return rc;
+    }
+    *out = h;
+    return 0;
+}
+
+int vip_upsample_run_f32(vip_upsample_t h, const float* d_src_lo, size_t src_pitch, const uint8_t* d_guide_lo,
+                         size_t guide_lo_pitch, const uint8_t* d_guide, size_t guide_pitch, int guide_channels,
+                         float* d_dst, size_t dst_pitch, void* stream) {
+    if (!h || !d_src_lo || !d_guide_lo || !d_guide || !d_dst) return VIP_ERR_INVALID_ARGUMENT;
+    if (guide_channels != 1 && guide_channels != 3) return VIP_ERR_INVALID_ARGUMENT;
+    if (!is_aligned(d_src_lo, src_pitch, 4) || !is_aligned(d_dst, dst_pitch, 4)) return VIP_ERR_INVALID_ARGUMENT;
+    const size_t gch = (size_t)guide_channels;
+    if (src_pitch < sizeof(float) * h->low_width || guide_lo_pitch < gch * h->low_width ||
+        guide_pitch < gch * h->width || dst_pitch < sizeof(float) * h->width)
+        return VIP_ERR_INVALID_ARGUMENT;
+    const void* const dst = d_dst;
+    if (dst == d_src_lo || dst == d_guide_lo || dst == d_guide) return VIP_ERR_ALIASING;
+    UpsampleArgs a{};
+    a.src = reinterpret_cast<const uint8_t*>(d_src_lo);
+    a.guide_lo = d_guide_lo;
+    a.guide = d_guide;
+    a.dst = reinterpret_cast<uint8_t*>(d_dst);
+    a.src_pitch = (long long)src_pitch;
+    a.guide_lo_pitch = (long long)guide_lo_pitch;
+    a.guide_pitch = (long long)guide_pitch;
+    a.dst_pitch = (long long)dst_pitch;
+    a.width = h->width;
+    a.out_rows = h->height;
+    a.low_width = h->low_width;
+    a.low_height = h->low_height;
+    a.aligned = (is_aligned(d_guide_lo, guide_lo_pitch, 4) ? kF32GuideWords : 0) |
+                (is_aligned(d_src_lo, src_pitch, 16) ? kF32SrcVec : 0) |
+                (is_aligned(d_guide, guide_pitch, 4) ? kUpGuideWords : 0);
+    a.dst_aligned = is_aligned(d_dst, dst_pitch, 16);
+    a.color = h->d_color;
+    a.wsp = h->d_wsp;
+    return launch_upsample_f32(h->radius, h->scale, guide_channels, h->numerics == VIP_NUMERICS_CUDA, a,
+                               (hipStream_t)stream);
 }
 
 // The frames of a *_run_rows_batch call, or a run of them

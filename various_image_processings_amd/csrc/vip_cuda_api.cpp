@@ -11,6 +11,7 @@
 
 #include "cuda/device_image.hpp"
 #include "cuda/gradient.hpp"
+#include "cuda/joint_bilateral_upsample.hpp"
 #include "impl/adaptive_bilateral_filter_impl.cuh"
 #include "impl/bilateral_filter_impl.cuh"
 #include "impl/bilateral_texture_filter_impl.cuh"
@@ -145,6 +146,32 @@ void CudaBilateralFilter::joint_bilateral_filter_f32(const float* const d_src, c
                                                      const int guide_channels, float* const d_dst,
                                                      void* stream) const {
     impl_->joint_bilateral_filter_f32(d_src, d_guide, guide_channels, d_dst, stream);
+}
+
+// ------------------------------------------------------------ CudaJointBilateralUpsample
+CudaJointBilateralUpsample::CudaJointBilateralUpsample(const int width, const int height, const int scale,
+                                                       const int ksize, const float sigma_space,
+                                                       const float sigma_color)
+    : width_(width) {
+    int rc = vip_upsample_create(&handle_, width, height, scale, ksize, sigma_space, sigma_color, VIP_NUMERICS_CUDA);
+    if (!rc) rc = vip_upsample_low_size(width, height, scale, &low_width_, &low_height_);
+    if (rc) fail("CudaJointBilateralUpsample", rc);
+}
+CudaJointBilateralUpsample::~CudaJointBilateralUpsample() { vip_upsample_destroy(handle_); }
+
+void CudaJointBilateralUpsample::upsample_f32(const float* const d_src_lo, const std::uint8_t* const d_guide_lo,
+                                              const std::uint8_t* const d_guide, const int guide_channels,
+                                              float* const d_dst, void* stream) const {
+    const size_t gch = guide_channels == 3 ? 3 : 1;
+    VIP_REPORT(vip_upsample_run_f32(handle_, d_src_lo, (size_t)low_width_ * sizeof(float), d_guide_lo,
+                                    (size_t)low_width_ * gch, d_guide, (size_t)width_ * gch, guide_channels, d_dst,
+                                    (size_t)width_ * sizeof(float), stream));
+}
+void CudaJointBilateralUpsample::upsample_f32(const float* const d_src_lo, const std::uint8_t* const d_guide_lo,
+                                              const std::uint8_t* const d_guide, const int guide_channels,
+                                              float* const d_dst) const {
+    upsample_f32(d_src_lo, d_guide_lo, d_guide, guide_channels, d_dst, nullptr);
+    VIP_REPORT(vip_device_synchronize());
 }
 
 // ------------------------------------------------------------ CudaAdaptiveBilateralFilter

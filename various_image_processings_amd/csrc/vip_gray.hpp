@@ -1,7 +1,8 @@
 // What the one-channel kernels share (vip_gray.hip: bilateral and joint bilateral;
 // vip_gray_adaptive.hip: adaptive bilateral; vip_joint_f32.hip: joint bilateral of an f32 source,
-// a guide and a float plane): the plane word of a pixel, the guide and tile loaders and the
-// register-staged tile prefetch (Guide4, GrayGroup, C1Prefetch), the byte-exact store, the forms
+// a guide and a float plane; vip_upsample.hip: joint bilateral upsampling, the same two planes at
+// low resolution): the plane word of a pixel, the guide and tile loaders and the register-staged
+// tile prefetch (Guide4, GrayGroup, F32Group, C1Prefetch), the byte-exact stores, the forms
 // of a tap's colour-LUT index (GraySad, GrayAdaptiveDist; F32Sad is vip_joint_f32.hip's) and, for
 // the radius-specialised kernels, the tap loop of one tile row (gray_row_taps) and the
 // one-plane kernels' row around it (gray_tile_row). The runtime-radius kernels' tile geometry
@@ -100,8 +101,63 @@ struct GrayGroup {
     }
 };
 
+// 4 pixels of one image row from column x (columns clamped to the image): the guide's 1 or 3
+// dwords and the source's 4 floats, as loaded from HBM, and as the plane words they become
+// (words(): the guide plane's; source_words(): the float plane's).
+template <int GUIDE>
+struct F32Group {
+    static constexpr bool TWO = true;
+    Guide4<GUIDE> g;
+    float4 f;
+
+    __device__ __forceinline__ void load(const uint8_t* src, long long src_pitch, const uint8_t* guide,
+                                         long long guide_pitch, int sy, int x, int width, int aligned) {
+        const bool interior = x >= 0 && x + 3 < width;
+        const float* frow = reinterpret_cast<const float*>(src + (long long)sy * src_pitch);
+        if ((aligned & kF32SrcVec) && interior) {
+            f = *reinterpret_cast<const float4*>(frow + x);
+        } else {
+            f.x = frow[clampi(x + 0, 0, width - 1)];
+            f.y = frow[clampi(x + 1, 0, width - 1)];
+            f.z = frow[clampi(x + 2, 0, width - 1)];
+            f.w = frow[clampi(x + 3, 0, width - 1)];
+        }
+        // with or without `interior` the flag means the same (Guide4 tests the columns itself); each
+        // guide form gets the spelling that compiles to the code it had (profiles/c1_shared_isa.txt)
+        const int gwords = aligned & kF32GuideWords;
+        g.load(guide + (long long)sy * guide_pitch, x, width, GUIDE == 3 ? (gwords && interior) : gwords);
+    }
+    __device__ __forceinline__ uint4 words() const {
+        if constexpr (GUIDE == 1)
+            return make_uint4(g.g0 & 0xffu, (g.g0 >> 8) & 0xffu, (g.g0 >> 16) & 0xffu, g.g0 >> 24);
+        return unpack_rgb4(g.g0, g.g1, g.g2);
+    }
+    __device__ __forceinline__ uint4 source_words() const {
+        return make_uint4(__float_as_uint(f.x), __float_as_uint(f.y), __float_as_uint(f.z), __float_as_uint(f.w));
+    }
+};
+
+// Write P float outputs of row oy from column x (a multiple of P): 16-byte stores where dst
+// allows them (dst_aligned: base and pitch are 16-byte aligned) and the outputs are all inside
+// the row, single dwords otherwise; never a byte at column >= width or row >= out_rows.
+template <int P, class A>
+__device__ __forceinline__ void store_f32(const A& a, int oy, int x, const float (&o)[P]) {
+    static_assert(P == 4 || P == 8, "outputs per thread");
+    if (oy >= a.out_rows || x >= a.width) return;
+    float* p = reinterpret_cast<float*>(a.dst + (long long)oy * a.dst_pitch) + x;
+    if (a.dst_aligned && x + P <= a.width) {
+#pragma unroll
+        for (int q = 0; q < P / 4; ++q)
+            reinterpret_cast<float4*>(p)[q] = make_float4(o[4 * q], o[4 * q + 1], o[4 * q + 2], o[4 * q + 3]);
+        return;
+    }
+#pragma unroll
+    for (int i = 0; i < P; ++i)
+        if (x + i < a.width) p[i] = o[i];
+}
+
 // Register-staged prefetch of one tile's plane or planes (TilePrefetch's one-channel form), in
-// GROUPs of 4 pixels (GrayGroup: one plane; vip_joint_f32.hip's F32Group: a guide and a float
+// GROUPs of 4 pixels (GrayGroup: one plane; F32Group: a guide and a float
 // plane): issue() starts the HBM loads of source rows [ty0 + src_row0 - R, +ROWS) x columns
 // [tx0 - L, tx0 + TW + L), rows clamped to [row_lo, row_hi), columns to [0, width); commit()
 // writes the plane words: the GROUP's words() and, with GROUP::TWO, its source_words() to fplane.

@@ -73,61 +73,6 @@ constexpr int f32_waves() {
                       16>();
 }
 
-// 4 pixels of one image row from column x (columns clamped to the image): the guide's 1 or 3
-// dwords and the source's 4 floats, as loaded from HBM, and as the plane words they become
-// (words(): the guide plane's; source_words(): the float plane's).
-template <int GUIDE>
-struct F32Group {
-    static constexpr bool TWO = true;
-    Guide4<GUIDE> g;
-    float4 f;
-
-    __device__ __forceinline__ void load(const uint8_t* src, long long src_pitch, const uint8_t* guide,
-                                         long long guide_pitch, int sy, int x, int width, int aligned) {
-        const bool interior = x >= 0 && x + 3 < width;
-        const float* frow = reinterpret_cast<const float*>(src + (long long)sy * src_pitch);
-        if ((aligned & kF32SrcVec) && interior) {
-            f = *reinterpret_cast<const float4*>(frow + x);
-        } else {
-            f.x = frow[clampi(x + 0, 0, width - 1)];
-            f.y = frow[clampi(x + 1, 0, width - 1)];
-            f.z = frow[clampi(x + 2, 0, width - 1)];
-            f.w = frow[clampi(x + 3, 0, width - 1)];
-        }
-        // with or without `interior` the flag means the same (Guide4 tests the columns itself); each
-        // guide form gets the spelling that compiles to the code it had (profiles/c1_shared_isa.txt)
-        const int gwords = aligned & kF32GuideWords;
-        g.load(guide + (long long)sy * guide_pitch, x, width, GUIDE == 3 ? (gwords && interior) : gwords);
-    }
-    __device__ __forceinline__ uint4 words() const {
-        if constexpr (GUIDE == 1)
-            return make_uint4(g.g0 & 0xffu, (g.g0 >> 8) & 0xffu, (g.g0 >> 16) & 0xffu, g.g0 >> 24);
-        return unpack_rgb4(g.g0, g.g1, g.g2);
-    }
-    __device__ __forceinline__ uint4 source_words() const {
-        return make_uint4(__float_as_uint(f.x), __float_as_uint(f.y), __float_as_uint(f.z), __float_as_uint(f.w));
-    }
-};
-
-// Write P float outputs of row oy from column x (a multiple of P): 16-byte stores where dst
-// allows them (dst_aligned: base and pitch are 16-byte aligned) and the outputs are all inside
-// the row, single dwords otherwise; never a byte at column >= width or row >= out_rows.
-template <int P, class A>
-__device__ __forceinline__ void store_f32(const A& a, int oy, int x, const float (&o)[P]) {
-    static_assert(P == 4 || P == 8, "outputs per thread");
-    if (oy >= a.out_rows || x >= a.width) return;
-    float* p = reinterpret_cast<float*>(a.dst + (long long)oy * a.dst_pitch) + x;
-    if (a.dst_aligned && x + P <= a.width) {
-#pragma unroll
-        for (int q = 0; q < P / 4; ++q)
-            reinterpret_cast<float4*>(p)[q] = make_float4(o[4 * q], o[4 * q + 1], o[4 * q + 2], o[4 * q + 3]);
-        return;
-    }
-#pragma unroll
-    for (int i = 0; i < P; ++i)
-        if (x + i < a.width) p[i] = o[i];
-}
-
 // A tap's colour-LUT index (as vip_gray.hpp's GraySad): the guide plane's word is the bare
 // guide, the float plane's word the neighbour's float as it stands.
 template <int GUIDE, int P>

@@ -110,6 +110,28 @@ constexpr int kF32GuideWords = 1;  // guide base and pitch are 4-byte aligned ->
 constexpr int kF32SrcVec = 2;      // source base and pitch are 16-byte aligned -> float4 loads
 int launch_joint_f32(int radius, int guide_channels, bool fma, const StencilArgs& a, hipStream_t s);
 int launch_joint_f32_rt(const RtArgs& a, int guide_channels, bool fma, hipStream_t s);
+// vip_upsample.hip: joint bilateral upsampling of a low-resolution f32 field (src, with the
+// low-resolution guide guide_lo beside it) under the full-resolution 8-bit guide; radius
+// 0..kUpMaxRadius in low-resolution pixels, scale 2, 4 or 8, guide_channels 1 or 3. src and dst
+// carry the float pointers, pitches in bytes; `aligned` is a set of kF32GuideWords and kF32SrcVec
+// (the low-resolution pair) and kUpGuideWords, dst_aligned as launch_joint_f32's.
+constexpr int kUpMaxRadius = 4;   // ksize <= 9
+constexpr int kUpGuideWords = 4;  // full-resolution guide base and pitch are 4-byte aligned -> dword loads
+struct UpsampleArgs {
+    const uint8_t* src;
+    const uint8_t* guide_lo;
+    const uint8_t* guide;
+    uint8_t* dst;
+    long long src_pitch, guide_lo_pitch, guide_pitch, dst_pitch;
+    int width, out_rows;          // the output frame (out_rows: its height)
+    int low_width, low_height;    // ceil(width / scale), ceil(out_rows / scale)
+    int tiles_x, tiles_total;     // set by the launcher
+    int aligned, dst_aligned;
+    const float* color;           // colour LUT in device memory (768 entries)
+    const float* wsp;             // [n][n], n = scale * radius + scale / 2: the spatial weight of the offset
+                                  // (2 ax + 1, 2 ay + 1) half pixels at [ay][ax]
+};
+int launch_upsample_f32(int radius, int scale, int guide_channels, bool fma, const UpsampleArgs& a, hipStream_t s);
 int launch_gradient_u8(const uint8_t* src, float* dst, int width, int height, int ch, hipStream_t stream);
 int launch_gradient_f32(const float* src, float* dst, int width, int height, int ch, bool fma, hipStream_t stream);
 int launch_blur_rtv(const uint8_t* img, const float* mag, float* blurred, float* rtv, int width, int height,

@@ -14,6 +14,10 @@ yuyuyu-bot/various_image_processings:
 * ``CudaBilateralTextureFilter(width, height, ksize=9, nitr=3).execute(d_src, d_dst)``
   (bilateral_texture_filter.hpp:9-12), and its one-channel form ``execute_c1(d_src, d_dst)`` (no reference
   counterpart)
+* ``CudaJointBilateralUpsample(width, height, scale, ksize=5, sigma_space=1., sigma_color=30.)`` with
+  ``upsample_f32(d_src_lo, d_guide_lo, d_guide, guide_channels, d_dst)``, ``low_width()`` and
+  ``low_height()``: a float32 field at 1/2, 1/4 or 1/8 scale brought up to the frame under the
+  full-resolution 8-bit guide (no reference counterpart)
 * ``cuda_gradient(d_src, d_dst, width, height, src_ch=1)`` (gradient.hpp:13-23)
 * ``DeviceImage(width, height, channels=1, dtype)`` with upload/download/get (device_image.hpp:4-16)
 
@@ -33,6 +37,7 @@ from ._lib import VIP_NUMERICS_CPP, VIP_NUMERICS_CUDA, VipError, call, lib
 
 __all__ = [
     "CudaBilateralFilter", "CudaAdaptiveBilateralFilter", "CudaBilateralTextureFilter", "cuda_gradient",
+    "CudaJointBilateralUpsample",
     "DeviceImage", "VipError", "VIP_NUMERICS_CUDA", "VIP_NUMERICS_CPP", "device_synchronize",
     "set_bilateral_waves", "set_bilateral_wide", "set_bilateral_frames_in_flight", "launched_kernels", "kernel_timing", "set_stencil_path", "max_ksize",
 ]
@@ -93,7 +98,7 @@ def set_stencil_path(path: int = _lib.VIP_PATH_AUTO) -> None:
 
 def max_ksize(filter_kind: int) -> int:
     """Largest ksize a filter accepts (include/vip.h vip_max_ksize): what the reference
-    runs -- bilateral 65, joint 47, adaptive 63, texture 24."""
+    runs -- bilateral 65, joint 47, adaptive 63, texture 24 -- and 9 for joint bilateral upsampling."""
     return int(lib().vip_max_ksize(int(filter_kind)))
 
 
@@ -291,6 +296,55 @@ class CudaBilateralFilter:
     def joint_bilateral_filter_f32(self, d_src, d_guide, guide_channels, d_dst):
         """float32 one-channel source under an 8-bit guide (include/vip.h vip_joint_bilateral_run_f32)."""
         self.impl_.joint_bilateral_filter_f32(d_src, d_guide, guide_channels, d_dst)
+        device_synchronize()
+
+
+class _UpsampleImpl(_Handle):
+    """Joint bilateral upsampling of a low-resolution f32 field under an 8-bit guide (include/vip.h
+    vip_upsample_*; no reference counterpart): no synchronisation."""
+    _destroy = "vip_upsample_destroy"
+
+    def __init__(self, width, height, scale, ksize=5, sigma_space=1.0, sigma_color=30.0, numerics=VIP_NUMERICS_CUDA):
+        super().__init__()
+        self.width, self.height, self.scale, self.ksize = int(width), int(height), int(scale), int(ksize)
+        call("vip_upsample_create", ctypes.byref(self._h), self.width, self.height, self.scale, self.ksize,
+             float(sigma_space), float(sigma_color), int(numerics))
+        lw, lh = ctypes.c_int(), ctypes.c_int()
+        call("vip_upsample_low_size", self.width, self.height, self.scale, ctypes.byref(lw), ctypes.byref(lh))
+        self._low = (lw.value, lh.value)
+
+    def low_width(self) -> int:
+        return self._low[0]
+
+    def low_height(self) -> int:
+        return self._low[1]
+
+    def upsample_f32(self, d_src_lo, d_guide_lo, d_guide, guide_channels, d_dst, stream=None):
+        """d_src_lo: low_width x low_height float32; d_guide_lo: the same size, uint8, gray
+        (guide_channels 1) or interleaved 3-channel (3); d_guide: width x height of the same
+        channel count; d_dst: width x height float32. All dense."""
+        gch = _BilateralImpl._guide_channels(guide_channels, "vip_upsample_run_f32")
+        (lw, lh), w, h = self._low, self.width, self.height
+        call("vip_upsample_run_f32", self._h, _ptr(d_src_lo, 4 * lw * lh, dtype="float32"), 4 * lw,
+             _ptr(d_guide_lo, lw * lh * gch), lw * gch, _ptr(d_guide, w * h * gch), w * gch, gch,
+             _ptr(d_dst, 4 * w * h, dtype="float32"), 4 * w, _stream(stream))
+
+
+class CudaJointBilateralUpsample:
+    """include/cuda/joint_bilateral_upsample.hpp; the public call blocks until done. scale 2, 4 or
+    8; ksize odd, 1..9, and sigma_space in low-resolution pixels."""
+
+    def __init__(self, width, height, scale, ksize=5, sigma_space=1.0, sigma_color=30.0, numerics=VIP_NUMERICS_CUDA):
+        self.impl_ = _UpsampleImpl(width, height, scale, ksize, sigma_space, sigma_color, numerics)
+
+    def low_width(self) -> int:
+        return self.impl_.low_width()
+
+    def low_height(self) -> int:
+        return self.impl_.low_height()
+
+    def upsample_f32(self, d_src_lo, d_guide_lo, d_guide, guide_channels, d_dst):
+        self.impl_.upsample_f32(d_src_lo, d_guide_lo, d_guide, guide_channels, d_dst)
         device_synchronize()
 
 
