@@ -46,6 +46,20 @@ public:
     void joint_bilateral_filter_f32(const float* const d_src, const std::uint8_t* const d_guide,
                                     const int guide_channels, float* const d_dst, void* stream) const;
 
+    // Confidence-weighted f32 form, which fills holes (include/vip.h
+    // vip_joint_bilateral_run_conf_f32): d_conf is a dense width x height float confidence
+    // (>= 0; 0 marks a hole, whose d_src value is ignored), hole_value what d_dst gets where no
+    // weight was in reach, d_weight (optional) the dense float sum of weights. ksize <= 31.
+    // Blocking, and with a stream non-blocking.
+    void joint_bilateral_filter_conf_f32(const float* const d_src, const float* const d_conf,
+                                         const std::uint8_t* const d_guide, const int guide_channels,
+                                         const float hole_value, float* const d_dst,
+                                         float* const d_weight = nullptr) const;
+    void joint_bilateral_filter_conf_f32(const float* const d_src, const float* const d_conf,
+                                         const std::uint8_t* const d_guide, const int guide_channels,
+                                         const float hole_value, float* const d_dst, float* const d_weight,
+                                         void* stream) const;
+
 protected:
     class Impl;  // defined in bilateral_filter_impl.cuh (test drivers reach it through impl_)
     std::unique_ptr<Impl> impl_;

@@ -38,6 +38,11 @@ public:
                                     const int guide_channels, float* const d_dst) const;
     void joint_bilateral_filter_f32(const float* const d_src, const std::uint8_t* const d_guide,
                                     const int guide_channels, float* const d_dst, void* stream) const;
+    // confidence-weighted f32 form (stream-ordered; the class's blocking overload synchronises)
+    void joint_bilateral_filter_conf_f32(const float* const d_src, const float* const d_conf,
+                                         const std::uint8_t* const d_guide, const int guide_channels,
+                                         const float hole_value, float* const d_dst, float* const d_weight,
+                                         void* stream) const;
 
     vip_bilateral_t handle() const { return handle_; }
 

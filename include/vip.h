@@ -72,12 +72,14 @@ int vip_max_radius(void);
  * Bilateral, joint and adaptive take odd ksize from 1 (radius 0: output = input for
  * sigma_space > 0); the texture filter any ksize from 1. The C++ and Python layers take
  * the same sets. Joint bilateral upsampling (no reference counterpart) takes odd ksize 1..9,
- * in low-resolution pixels. Returns VIP_ERR_INVALID_ARGUMENT for an unknown filter. */
+ * in low-resolution pixels; the confidence-weighted f32 joint bilateral (VIP_FILTER_JOINT_CONF) odd
+ * ksize 1..31. Returns VIP_ERR_INVALID_ARGUMENT for an unknown filter. */
 #define VIP_FILTER_BILATERAL 0
 #define VIP_FILTER_JOINT 1
 #define VIP_FILTER_ADAPTIVE 2
 #define VIP_FILTER_TEXTURE 3
 #define VIP_FILTER_UPSAMPLE 4
+#define VIP_FILTER_JOINT_CONF 5
 int vip_max_ksize(int filter);
 
 /* Kernel selection, process-wide (no reference counterpart; results are identical either
@@ -228,6 +230,48 @@ int vip_joint_bilateral_run_rows_f32(vip_bilateral_t h, const float* d_src, size
                                      const uint8_t* d_guide, size_t guide_pitch, int guide_channels, float* d_dst,
                                      size_t dst_pitch, int out_rows, int src_row0, int row_lo, int row_hi,
                                      void* stream);
+/* ---- confidence-weighted joint bilateral of an f32 one-channel source (normalised convolution
+ * under an image guide; no counterpart in the reference's API): a field f with holes or with a
+ * per-pixel confidence c is smoothed under the 8-bit guide G, and pixels without a valid value are
+ * filled from the valid ones in reach. With a 0/1 mask as c it is hole filling, with a solver's
+ * confidence the usual confidence-weighted refinement. ws, wc, the row-major tap order over the
+ * k x k square, the replicate border and d are those of vip_joint_bilateral_run_f32.
+ * Per pixel, formed once:
+ *   p = (c == 0) ? +0.0f : f * c     one binary32 product; f is not used as a number where c == 0
+ * Per output pixel and tap:
+ *   w    = ws[ky,kx] * wc[d]
+ *   s    = fmaf(p_n, w, s)    sumk = fmaf(c_n, w, sumk)      VIP_NUMERICS_CUDA
+ *   s    = s + p_n * w        sumk = sumk + c_n * w          VIP_NUMERICS_CPP (two roundings each)
+ *   dst    = (sumk == 0) ? hole_value : s / sumk             IEEE binary32 division
+ *   weight = sumk                                            written only if d_weight != NULL
+ * Arithmetic is binary32 with gradual underflow (denormal mode 3, as the sibling kernels).
+ * Domain: c is finite and >= 0 (-0.0f counts as 0); f is finite wherever c > 0. Where c == 0, f may
+ * hold anything, NaN and Inf included: the output is, bit for bit, independent of it. Outside the
+ * domain the values are unspecified, but the call cannot fault: every address comes from
+ * coordinates and the guide.
+ * Ties that hold bit for bit: with c == 1 everywhere dst equals vip_joint_bilateral_run_f32 on f
+ * (p = f and fmaf(1, w, sumk) = sumk + w); with c == 2^-2 everywhere dst is the same as with
+ * c == 1, on inputs free of underflow.
+ * ksize 1..31 odd (vip_max_ksize(VIP_FILTER_JOINT_CONF)); a handle with a larger ksize gives
+ * VIP_ERR_UNSUPPORTED_KSIZE. The cap: the filter keeps three LDS planes (guide word, p, c) where
+ * the f32 filter keeps two, and three planes under the runtime-radius kernel's 64 x 64 tile stop
+ * fitting LDS near radius 12..16, so there is no runtime-radius kernel here; depth and disparity
+ * refinement lives at these sizes. ksize 1 gives dst = c == 0 ? hole_value : fl(f * c) / c.
+ * vip_set_stencil_path and the vip_bilateral_set_* knobs do not apply.
+ * Pitches are in bytes. The float bases and pitches (d_src, d_conf, d_dst, d_weight) must be
+ * multiples of 4; 16-byte accesses are used only where base and pitch allow them, decided per
+ * array. d_guide may have any base and pitch. No byte of d_dst or d_weight at column >= width or
+ * row >= height is written. VIP_ERR_INVALID_ARGUMENT: null handle, d_src, d_conf, d_guide or
+ * d_dst; guide_channels not 1 or 3; a misaligned float base or pitch; a pitch smaller than a row.
+ * VIP_ERR_ALIASING: d_dst or d_weight equals any input, or the two are equal. One launch per call,
+ * no device allocation: vip::joint_conf_f32_kernel<R, GUIDE, FMA> for radius 1..15,
+ * vip::joint_conf_f32_k1_kernel<FMA> for ksize 1; the launch log and vip_kernel_timing_* see them.
+ * Against today's route (two vip_joint_bilateral_run_f32 launches on f * c and c, two elementwise
+ * passes): see DESIGN.md section 4 for the measured times; nothing here promises a speed. */
+int vip_joint_bilateral_run_conf_f32(vip_bilateral_t h, const float* d_src, size_t src_pitch, const float* d_conf,
+                                     size_t conf_pitch, const uint8_t* d_guide, size_t guide_pitch,
+                                     int guide_channels, float hole_value, float* d_dst, size_t dst_pitch,
+                                     float* d_weight /* may be NULL */, size_t weight_pitch, void* stream);
 /* ---- joint bilateral upsampling (Kopf et al. 2007; no counterpart in the reference's API): a
  * field f solved at 1/2, 1/4 or 1/8 scale is brought up to the frame under the full-resolution
  * image, in one launch, with no full-resolution float intermediate.

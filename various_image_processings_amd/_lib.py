@@ -21,6 +21,7 @@ VIP_ERR_UNSUPPORTED_KSIZE = 10002
 VIP_ERR_ALIASING = 10003
 VIP_FILTER_BILATERAL, VIP_FILTER_JOINT, VIP_FILTER_ADAPTIVE, VIP_FILTER_TEXTURE = 0, 1, 2, 3
 VIP_FILTER_UPSAMPLE = 4
+VIP_FILTER_JOINT_CONF = 5
 VIP_PATH_AUTO, VIP_PATH_RUNTIME = 0, 1
 
 _c_void_p = ctypes.c_void_p
@@ -82,6 +83,9 @@ SIGNATURES = {
     "vip_joint_bilateral_run_rows_f32": (
         _c_int, [_c_void_p, _c_void_p, _c_size_t, _c_void_p, _c_size_t, _c_int, _c_void_p, _c_size_t,
                  _c_int, _c_int, _c_int, _c_int, _c_void_p]),
+    "vip_joint_bilateral_run_conf_f32": (
+        _c_int, [_c_void_p, _c_void_p, _c_size_t, _c_void_p, _c_size_t, _c_void_p, _c_size_t, _c_int, _c_float,
+                 _c_void_p, _c_size_t, _c_void_p, _c_size_t, _c_void_p]),
     "vip_upsample_create": (
         _c_int, [ctypes.POINTER(_c_void_p), _c_int, _c_int, _c_int, _c_int, _c_float, _c_float, _c_int]),
     "vip_upsample_destroy": (_c_int, [_c_void_p]),

@@ -96,6 +96,8 @@ static void build_color(int len, float sigma_color, int numerics, float* out) {
 constexpr int kMaxKsizeBilateral = 65, kMaxKsizeJoint = 47, kMaxKsizeAdaptive = 63, kMaxKsizeTexture = 24;
 // joint bilateral upsampling has no reference counterpart: its ksize counts low-resolution pixels
 constexpr int kMaxKsizeUpsample = 2 * kUpMaxRadius + 1;
+// the confidence-weighted f32 joint filter has the radius-specialised kernels only (three LDS planes)
+constexpr int kMaxKsizeJointConf = 2 * kMaxRadius + 1;
 static bool valid_ksize(int ksize, int max_ksize) { return ksize >= 1 && (ksize & 1) && ksize <= max_ksize; }
 
 // vip_set_stencil_path: VIP_PATH_AUTO (templated kernels for radius 1..15, the
@@ -484,6 +486,7 @@ int vip_max_ksize(int filter) {
         case VIP_FILTER_ADAPTIVE: return kMaxKsizeAdaptive;
         case VIP_FILTER_TEXTURE: return kMaxKsizeTexture;
         case VIP_FILTER_UPSAMPLE: return kMaxKsizeUpsample;
+        case VIP_FILTER_JOINT_CONF: return kMaxKsizeJointConf;
         default: return VIP_ERR_INVALID_ARGUMENT;
     }
 }
@@ -517,8 +520,8 @@ const char* vip_error_string(int code) {
         case 0: return "success";
         case VIP_ERR_INVALID_ARGUMENT: return "invalid argument";
         case VIP_ERR_UNSUPPORTED_KSIZE:
-            return "unsupported ksize (odd, 1..65 bilateral, 1..47 joint bilateral, 1..63 adaptive, 1..9 upsampling; "
-                   "texture 1..24)";
+            return "unsupported ksize (odd, 1..65 bilateral, 1..47 joint bilateral, 1..63 adaptive, 1..9 upsampling, 1..31 confidence-weighted "
+                   "joint; texture 1..24)";
         case VIP_ERR_ALIASING: return "source and destination alias";
         default: return hipGetErrorString((hipError_t)code);
     }
@@ -671,6 +674,43 @@ int vip_joint_bilateral_run_f32(vip_bilateral_t h, const float* d_src, size_t sr
     if (!h) return VIP_ERR_INVALID_ARGUMENT;
     return vip_joint_bilateral_run_rows_f32(h, d_src, src_pitch, d_guide, guide_pitch, guide_channels, d_dst,
                                             dst_pitch, h->height, 0, 0, h->height, stream);
+}
+
+// ---- confidence-weighted form of the f32 joint filter (vip_joint_conf.hip): the whole frame, the
+// radius-specialised kernels only; each float array's 16-byte accesses are decided on its own
+int vip_joint_bilateral_run_conf_f32(vip_bilateral_t h, const float* d_src, size_t src_pitch, const float* d_conf,
+                                     size_t conf_pitch, const uint8_t* d_guide, size_t guide_pitch,
+                                     int guide_channels, float hole_value, float* d_dst, size_t dst_pitch,
+                                     float* d_weight, size_t weight_pitch, void* stream) {
+    if (!h || !d_src || !d_conf || !d_guide || !d_dst) return VIP_ERR_INVALID_ARGUMENT;
+    if (guide_channels != 1 && guide_channels != 3) return VIP_ERR_INVALID_ARGUMENT;
+    if (!is_aligned(d_src, src_pitch, 4) || !is_aligned(d_conf, conf_pitch, 4) || !is_aligned(d_dst, dst_pitch, 4) ||
+        (d_weight && !is_aligned(d_weight, weight_pitch, 4)))
+        return VIP_ERR_INVALID_ARGUMENT;
+    const size_t frow = sizeof(float) * (size_t)h->width;
+    if (src_pitch < frow || conf_pitch < frow || dst_pitch < frow || (d_weight && weight_pitch < frow) ||
+        guide_pitch < (size_t)guide_channels * (size_t)h->width)
+        return VIP_ERR_INVALID_ARGUMENT;
+    const void* const ins[3] = {d_src, d_conf, d_guide};
+    for (const void* in : ins)
+        if (in == d_dst || in == d_weight) return VIP_ERR_ALIASING;
+    if (d_dst == d_weight) return VIP_ERR_ALIASING;
+    if (h->ksize > kMaxKsizeJointConf) return VIP_ERR_UNSUPPORTED_KSIZE;
+    const RowBand b{reinterpret_cast<const uint8_t*>(d_src), src_pitch, d_guide, guide_pitch,
+                    reinterpret_cast<uint8_t*>(d_dst), dst_pitch, h->height, 0, 0, h->height};
+    ConfArgs a;
+    static_cast<StencilArgs&>(a) = stencil_args(*h, b);
+    a.aligned = (is_aligned(d_guide, guide_pitch, 4) ? kF32GuideWords : 0) |
+                (is_aligned(d_src, src_pitch, 16) ? kF32SrcVec : 0);
+    a.dst_aligned = is_aligned(d_dst, dst_pitch, 16);
+    a.conf = reinterpret_cast<const uint8_t*>(d_conf);
+    a.conf_pitch = (long long)conf_pitch;
+    a.conf_vec = is_aligned(d_conf, conf_pitch, 16);
+    a.weight = reinterpret_cast<uint8_t*>(d_weight);
+    a.weight_pitch = (long long)weight_pitch;
+    a.weight_aligned = d_weight && is_aligned(d_weight, weight_pitch, 16);
+    a.hole_value = hole_value;
+    return launch_joint_conf_f32(h->radius, guide_channels, h->numerics == VIP_NUMERICS_CUDA, a, (hipStream_t)stream);
 }
 
 // ---- joint bilateral upsampling (vip_upsample.hip): a handle of its own, since the spatial

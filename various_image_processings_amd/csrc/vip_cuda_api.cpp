@@ -92,6 +92,16 @@ void CudaBilateralFilter::Impl::joint_bilateral_filter_f32(const float* const d_
                                            pitch * (size_t)(guide_channels == 3 ? 3 : 1), guide_channels, d_dst,
                                            pitch * sizeof(float), stream));
 }
+void CudaBilateralFilter::Impl::joint_bilateral_filter_conf_f32(const float* const d_src, const float* const d_conf,
+                                                                const std::uint8_t* const d_guide,
+                                                                const int guide_channels, const float hole_value,
+                                                                float* const d_dst, float* const d_weight,
+                                                                void* stream) const {
+    const size_t pitch = (size_t)width_, fp = pitch * sizeof(float);
+    VIP_REPORT(vip_joint_bilateral_run_conf_f32(handle_, d_src, fp, d_conf, fp, d_guide,
+                                                pitch * (size_t)(guide_channels == 3 ? 3 : 1), guide_channels,
+                                                hole_value, d_dst, fp, d_weight, fp, stream));
+}
 
 CudaBilateralFilter::CudaBilateralFilter(const int width, const int height, const int ksize, const float sigma_space,
                                          const float sigma_color)
@@ -146,6 +156,21 @@ void CudaBilateralFilter::joint_bilateral_filter_f32(const float* const d_src, c
                                                      const int guide_channels, float* const d_dst,
                                                      void* stream) const {
     impl_->joint_bilateral_filter_f32(d_src, d_guide, guide_channels, d_dst, stream);
+}
+void CudaBilateralFilter::joint_bilateral_filter_conf_f32(const float* const d_src, const float* const d_conf,
+                                                          const std::uint8_t* const d_guide, const int guide_channels,
+                                                          const float hole_value, float* const d_dst,
+                                                          float* const d_weight) const {
+    impl_->joint_bilateral_filter_conf_f32(d_src, d_conf, d_guide, guide_channels, hole_value, d_dst, d_weight,
+                                           nullptr);
+    VIP_REPORT(vip_device_synchronize());
+}
+void CudaBilateralFilter::joint_bilateral_filter_conf_f32(const float* const d_src, const float* const d_conf,
+                                                          const std::uint8_t* const d_guide, const int guide_channels,
+                                                          const float hole_value, float* const d_dst,
+                                                          float* const d_weight, void* stream) const {
+    impl_->joint_bilateral_filter_conf_f32(d_src, d_conf, d_guide, guide_channels, hole_value, d_dst, d_weight,
+                                           stream);
 }
 
 // ------------------------------------------------------------ CudaJointBilateralUpsample

@@ -156,19 +156,35 @@ __device__ __forceinline__ void store_f32(const A& a, int oy, int x, const float
         if (x + i < a.width) p[i] = o[i];
 }
 
+// A third plane is a policy of the GROUP (the tile loaders) and of the DIST (the tap loop): a
+// type that declares THREE = true (vip_joint_conf.hip's ConfGroup and ConfSad: a confidence
+// plane beside the guide and source planes). Every other type has two planes at most, and the
+// third-plane text below is discarded for it at compile time.
+template <class T>
+constexpr bool has_third_plane() {
+    if constexpr (requires { T::THREE; })
+        return T::THREE;
+    else
+        return false;
+}
+
 // Register-staged prefetch of one tile's plane or planes (TilePrefetch's one-channel form), in
 // GROUPs of 4 pixels (GrayGroup: one plane; F32Group: a guide and a float
-// plane): issue() starts the HBM loads of source rows [ty0 + src_row0 - R, +ROWS) x columns
+// plane; a three-plane GROUP: a confidence plane as well): issue() starts the HBM loads of source rows [ty0 + src_row0 - R, +ROWS) x columns
 // [tx0 - L, tx0 + TW + L), rows clamped to [row_lo, row_hi), columns to [0, width); commit()
-// writes the plane words: the GROUP's words() and, with GROUP::TWO, its source_words() to fplane.
+// writes the plane words: the GROUP's words() and, with GROUP::TWO, its source_words() to fplane
+// (a three-plane GROUP: its conf_words() to cplane too; such a GROUP loads from the kernel's own
+// argument struct, which holds the third array).
 template <int R, int ROWS, int NT, int P, class GROUP>
 struct C1Prefetch {
     using G = Geom<R, P, 16>;
     static constexpr int NG = ROWS * G::GROUPS;
     static constexpr int K = (NG + NT - 1) / NT;
+    static constexpr bool THREE = has_third_plane<GROUP>();
     GROUP raw[K];
 
-    __device__ __forceinline__ void issue(const StencilArgs& a, int tx0, int ty0) {
+    template <class ARGS>
+    __device__ __forceinline__ void issue(const ARGS& a, int tx0, int ty0) {
 #pragma unroll
         for (int k = 0; k < K; ++k) {
             const int g = (int)threadIdx.x + k * NT;
@@ -176,10 +192,14 @@ struct C1Prefetch {
             const int r = g / G::GROUPS;
             const int gc = g - r * G::GROUPS;
             const int sy = clampi(ty0 + a.src_row0 - R + r, a.row_lo, a.row_hi - 1);
-            raw[k].load(a.src, a.src_pitch, a.guide, a.guide_pitch, sy, tx0 - G::L + 4 * gc, a.width, a.aligned);
+            if constexpr (THREE)
+                raw[k].load(a, sy, tx0 - G::L + 4 * gc);
+            else
+                raw[k].load(a.src, a.src_pitch, a.guide, a.guide_pitch, sy, tx0 - G::L + 4 * gc, a.width, a.aligned);
         }
     }
-    __device__ __forceinline__ void commit(uint32_t* plane, uint32_t* fplane = nullptr) const {
+    __device__ __forceinline__ void commit(uint32_t* plane, uint32_t* fplane = nullptr,
+                                           uint32_t* cplane = nullptr) const {
 #pragma unroll
         for (int k = 0; k < K; ++k) {
             const int g = (int)threadIdx.x + k * NT;
@@ -188,6 +208,7 @@ struct C1Prefetch {
             const int gc = g - r * G::GROUPS;
             *reinterpret_cast<uint4*>(plane + r * G::S + 4 * gc) = raw[k].words();
             if constexpr (GROUP::TWO) *reinterpret_cast<uint4*>(fplane + r * G::S + 4 * gc) = raw[k].source_words();
+            if constexpr (THREE) *reinterpret_cast<uint4*>(cplane + r * G::S + 4 * gc) = raw[k].conf_words();
         }
     }
 };
@@ -245,27 +266,49 @@ struct GrayAdaptiveDist {
     }
 };
 
+// The third plane's words of one tile row beside a RowStream, read chunk by chunk with it (a
+// RowStream of the one plane); nothing at all without a third plane.
+template <int C0, int NC, bool THREE>
+struct ThirdRow {
+    __device__ __forceinline__ ThirdRow(const uint32_t*, int) {}
+    __device__ __forceinline__ void load(int) {}
+};
+template <int C0, int NC>
+struct ThirdRow<C0, NC, true> {
+    RowStream<C0, NC, false> row;
+    __device__ __forceinline__ ThirdRow(const uint32_t* cplane, int row_off) : row(cplane, cplane, row_off) {}
+    __device__ __forceinline__ void load(int q) { row.load(q); }
+    __device__ __forceinline__ float word(int k) const { return __uint_as_float(row.guide(k)); }
+};
+
 // The tap loop of one tile row (row_taps' one-accumulator form): neighbour column j serves
 // output i at kx = j - L - i; per output the taps run in ascending kx. fplane: the source's
-// plane when DIST::TWO, else not read (the callers pass plane again).
+// plane when DIST::TWO, else not read (the callers pass plane again). cplane: read only by a
+// three-plane DIST (has_third_plane): the plane of the neighbour's confidence c_n, and the
+// weight sum is then sumk = fma(c_n, w, sumk) (sumk + c_n * w without FMA) instead of sumk + w.
 template <int HW, int L, int C0, int NC, bool FMA, int P, class DIST>
 __device__ __forceinline__ void gray_row_taps(const uint32_t* plane, const uint32_t* fplane, int row_off,
                                               const float (&wsv)[HW + 1], const char* lut, uint32_t lane4,
-                                              const DIST& dist, float (&s)[P], float (&sk)[P]) {
+                                              const DIST& dist, float (&s)[P], float (&sk)[P],
+                                              const uint32_t* cplane = nullptr) {
     constexpr int D = kPipeDepth, NB = D + 1;
     constexpr int J0 = L - HW, J1 = L + P - 1 + HW;
     constexpr int LA = D + kRowLookahead;
+    constexpr bool THREE = has_third_plane<DIST>();
     static_assert(J0 >= 4 * C0 && J1 < 4 * (C0 + NC), "row chunk range");
     auto chunk = [](int j) constexpr { return (j - 4 * C0) >> 2; };
     constexpr int PRE = chunk(J0 + LA < J1 ? J0 + LA : J1);
     RowStream<C0, NC, DIST::TWO> row(plane, fplane, row_off);
+    ThirdRow<C0, NC, THREE> crow(cplane, row_off);
 #pragma unroll
-    for (int q = 0; q <= PRE; ++q) row.load(q);
+    for (int q = 0; q <= PRE; ++q) row.load(q), crow.load(q);
     float wc[NB][P], nf[NB];
+    [[maybe_unused]] float nc[NB];
     auto issue = [&](int j) {
         const uint32_t g = DIST::guide(row.guide(j - 4 * C0));
         const int b = (j - J0) % NB;
         nf[b] = DIST::source(row.source(j - 4 * C0));
+        if constexpr (THREE) nc[b] = crow.word(j - 4 * C0);
 #pragma unroll
         for (int i = 0; i < P; ++i) {
             const int kx = j - L - i;
@@ -278,7 +321,7 @@ __device__ __forceinline__ void gray_row_taps(const uint32_t* plane, const uint3
     for (int j = J0; j < J0 + D && j <= J1; ++j) issue(j);
 #pragma unroll
     for (int j = J0; j <= J1; ++j) {
-        if (j + LA <= J1 && ((j + LA) & 3) == 0 && chunk(j + LA) > PRE) row.load(chunk(j + LA));
+        if (j + LA <= J1 && ((j + LA) & 3) == 0 && chunk(j + LA) > PRE) row.load(chunk(j + LA)), crow.load(chunk(j + LA));
         if (j + D <= J1) issue(j + D);
         const int b = (j - J0) % NB;
 #pragma unroll
@@ -290,7 +333,12 @@ __device__ __forceinline__ void gray_row_taps(const uint32_t* plane, const uint3
                 s[i] = __builtin_fmaf(nf[b], w, s[i]);
             else
                 s[i] = s[i] + nf[b] * w;
-            sk[i] = sk[i] + w;
+            if constexpr (!THREE)
+                sk[i] = sk[i] + w;
+            else if constexpr (FMA)
+                sk[i] = __builtin_fmaf(nc[b], w, sk[i]);
+            else
+                sk[i] = sk[i] + nc[b] * w;
         }
         __builtin_amdgcn_sched_barrier(0);
     }

@@ -132,6 +132,19 @@ struct UpsampleArgs {
                                   // (2 ax + 1, 2 ay + 1) half pixels at [ay][ax]
 };
 int launch_upsample_f32(int radius, int scale, int guide_channels, bool fma, const UpsampleArgs& a, hipStream_t s);
+// vip_joint_conf.hip: the confidence-weighted form of launch_joint_f32 (radius 0..15, no
+// runtime-radius kernel). StencilArgs as launch_joint_f32 reads it (one whole frame), plus the
+// confidence plane, the optional weight output and the value written where no weight was in reach;
+// the struct is this kernel's alone, so every other kernel's arguments stay what they are.
+struct ConfArgs : StencilArgs {
+    const uint8_t* conf;   // f32 confidence, pitch in bytes
+    uint8_t* weight;       // f32 sum of weights, or null
+    long long conf_pitch, weight_pitch;
+    float hole_value;
+    int conf_vec;          // conf base and pitch are 16-byte aligned -> float4 loads
+    int weight_aligned;    // weight base and pitch are 16-byte aligned -> float4 stores
+};
+int launch_joint_conf_f32(int radius, int guide_channels, bool fma, const ConfArgs& a, hipStream_t s);
 int launch_gradient_u8(const uint8_t* src, float* dst, int width, int height, int ch, hipStream_t stream);
 int launch_gradient_f32(const float* src, float* dst, int width, int height, int ch, bool fma, hipStream_t stream);
 int launch_blur_rtv(const uint8_t* img, const float* mag, float* blurred, float* rtv, int width, int height,
@@ -260,9 +273,11 @@ inline void plan_tail(StencilArgs& a, int blocks, int waves) {
 // KERN for one frame, FRAMES_KERN for a.nframes > 1 (nullptr: no multi-frame form, a.nframes
 // is not looked at and the caller refuses such a launch), LDS bytes of dynamic LDS (ABS_LDS:
 // see ensure_dynamic_lds), WAVES waves per workgroup, TW x TH pixel tiles. cut_tail: a
-// multi-frame launch runs its last round in pieces (plan_tail).
-template <auto KERN, auto FRAMES_KERN, int LDS, int WAVES, int TW, int TH, bool ABS_LDS>
-static int launch_persistent(const StencilArgs& a, bool cut_tail, hipStream_t stream) {
+// multi-frame launch runs its last round in pieces (plan_tail). ARGS: the kernel's argument struct,
+// StencilArgs or one derived from it (ConfArgs), copied whole.
+template <auto KERN, auto FRAMES_KERN, int LDS, int WAVES, int TW, int TH, bool ABS_LDS, class ARGS>
+static int launch_persistent(const ARGS& a, bool cut_tail, hipStream_t stream) {
+    static_assert(std::is_base_of_v<StencilArgs, ARGS>, "kernel arguments");
     constexpr bool HAS_FRAMES = !std::is_null_pointer_v<decltype(FRAMES_KERN)>;
     const bool multi = HAS_FRAMES && a.nframes > 1;
     auto kern = KERN;
@@ -273,7 +288,7 @@ static int launch_persistent(const StencilArgs& a, bool cut_tail, hipStream_t st
     if (!multi) rc = ensure_lds<KERN>(LDS, ABS_LDS);
     if (rc) return rc;
     note_launch(reinterpret_cast<const void*>(kern));
-    StencilArgs args = a;
+    ARGS args = a;
     args.tiles_x = (a.width + TW - 1) / TW;
     args.tiles_frame = args.tiles_x * ((a.out_rows + TH - 1) / TH);
     args.tiles_total = args.tiles_frame * (multi ? a.nframes : 1);
@@ -288,8 +303,8 @@ static int launch_persistent(const StencilArgs& a, bool cut_tail, hipStream_t st
 
 // The one-channel kernels' persistent launch: one frame, whole tiles of G::TW x WAVES * G::RPW
 // pixels (G: the kernel's Geom), no absolute LDS address.
-template <auto KERN, int LDS, int WAVES, class G>
-static int launch_c1_tiles(const StencilArgs& a, hipStream_t stream) {
+template <auto KERN, int LDS, int WAVES, class G, class ARGS>
+static int launch_c1_tiles(const ARGS& a, hipStream_t stream) {
     static_assert(LDS <= kLdsBudget, "tile does not fit LDS");
     return launch_persistent<KERN, nullptr, LDS, WAVES, G::TW, WAVES * G::RPW, false>(a, false, stream);
 }

@@ -8,7 +8,9 @@ yuyuyu-bot/various_image_processings:
   (include/cuda/bilateral_filter.hpp:9-24), and their one-channel forms ``bilateral_filter_c1(d_src,
   d_dst)`` / ``joint_bilateral_filter_c1(d_src, d_guide, guide_channels, d_dst)`` (no reference counterpart),
   and ``joint_bilateral_filter_f32(d_src, d_guide, guide_channels, d_dst)``: a float32 one-channel source
-  and destination under an 8-bit guide (no reference counterpart)
+  and destination under an 8-bit guide (no reference counterpart), and its confidence-weighted form
+  ``joint_bilateral_filter_conf_f32(d_src, d_conf, d_guide, guide_channels, d_dst, hole_value=0.,
+  d_weight=None)``, which fills holes (ksize <= 31)
 * ``CudaAdaptiveBilateralFilter(...).execute(d_src, d_dst)`` (adaptive_bilateral_filter.hpp:9-19), and its
   one-channel form ``execute_c1(d_src, d_dst)`` (no reference counterpart)
 * ``CudaBilateralTextureFilter(width, height, ksize=9, nitr=3).execute(d_src, d_dst)``
@@ -98,7 +100,8 @@ def set_stencil_path(path: int = _lib.VIP_PATH_AUTO) -> None:
 
 def max_ksize(filter_kind: int) -> int:
     """Largest ksize a filter accepts (include/vip.h vip_max_ksize): what the reference
-    runs -- bilateral 65, joint 47, adaptive 63, texture 24 -- and 9 for joint bilateral upsampling."""
+    runs -- bilateral 65, joint 47, adaptive 63, texture 24 -- and 9 for joint bilateral upsampling, 31 for the
+    confidence-weighted f32 joint filter."""
     return int(lib().vip_max_ksize(int(filter_kind)))
 
 
@@ -253,6 +256,18 @@ class _BilateralImpl(_Handle):
              _ptr(d_guide, p * gch * int(row_hi)), p * gch, gch, _ptr(d_dst, 4 * p * int(out_rows), dtype="float32"),
              4 * p, int(out_rows), int(src_row0), int(row_lo), int(row_hi), _stream(stream))
 
+    def joint_bilateral_filter_conf_f32(self, d_src, d_conf, d_guide, guide_channels, d_dst, hole_value=0.0,
+                                        d_weight=None, stream=None):
+        """Confidence-weighted f32 form, which fills holes (include/vip.h
+        vip_joint_bilateral_run_conf_f32): d_conf is width * height float32, >= 0, 0 marking a hole;
+        d_dst gets hole_value where no weight was in reach; d_weight (optional) the sum of weights."""
+        gch = self._guide_channels(guide_channels, "vip_joint_bilateral_run_conf_f32")
+        p, n = self.width, self.width * self.height
+        wgt = None if d_weight is None else _ptr(d_weight, 4 * n, dtype="float32")
+        call("vip_joint_bilateral_run_conf_f32", self._h, _ptr(d_src, 4 * n, dtype="float32"), 4 * p,
+             _ptr(d_conf, 4 * n, dtype="float32"), 4 * p, _ptr(d_guide, n * gch), p * gch, gch, float(hole_value),
+             _ptr(d_dst, 4 * n, dtype="float32"), 4 * p, wgt, 4 * p, _stream(stream))
+
     def run_rows_batch(self, d_srcs, d_dsts, out_rows, src_row0, row_lo, row_hi, free_cus=0, stream=None):
         """run_rows over several frames of the same geometry, up to 6 per launch
         (include/vip.h vip_bilateral_run_rows_batch)."""
@@ -296,6 +311,13 @@ class CudaBilateralFilter:
     def joint_bilateral_filter_f32(self, d_src, d_guide, guide_channels, d_dst):
         """float32 one-channel source under an 8-bit guide (include/vip.h vip_joint_bilateral_run_f32)."""
         self.impl_.joint_bilateral_filter_f32(d_src, d_guide, guide_channels, d_dst)
+        device_synchronize()
+
+    def joint_bilateral_filter_conf_f32(self, d_src, d_conf, d_guide, guide_channels, d_dst, hole_value=0.0,
+                                        d_weight=None):
+        """Confidence-weighted f32 form, which fills holes (include/vip.h vip_joint_bilateral_run_conf_f32)."""
+        self.impl_.joint_bilateral_filter_conf_f32(d_src, d_conf, d_guide, guide_channels, d_dst, hole_value,
+                                                   d_weight)
         device_synchronize()
 
 
