@@ -6,6 +6,7 @@ oracle) bit for bit, in both numerics profiles and under both kernel selections:
 radius-specialised vip::gray_kernel (128 x 64 tiles, radius 1..15) and the runtime-radius
 vip::gray_rt_kernel (64 x 64 tiles; radius 0 and 16..32, or every radius under
 VIP_PATH_RUNTIME).
+Frames of more tiles than the device has CUs (gray_kernel's later rounds): tests/test_gpu_c1_rounds.py.
 """
 import ctypes
 import functools

@@ -6,6 +6,7 @@ Bar: every output equals tests/gray_adaptive_oracle.py (the embedding (g, 0, 0) 
 selections: the radius-specialised vip::gray_adaptive_kernel (128 x 64 tiles, radius 1..15) and
 the runtime-radius vip::gray_adaptive_rt_kernel (64 x 64 tiles; radius 0 and 16..31, or every
 radius under VIP_PATH_RUNTIME).
+Frames of more tiles than the device has CUs (gray_adaptive_kernel's later rounds): tests/test_gpu_c1_rounds.py.
 """
 import functools
 

@@ -4,6 +4,7 @@ an 8-bit guide (csrc/vip_joint_conf.hip; include/vip.h vip_joint_bilateral_run_c
 Bar: dst and the weight output equal tests/conf_oracle.py bit for bit (compared as uint32), in both
 numerics profiles, with a gray and with a 3-channel guide, and dst is the same bits with and
 without the weight output.
+Frames of more tiles than the device has CUs (joint_conf_f32_kernel's later rounds): tests/test_gpu_c1_rounds.py.
 """
 import functools
 import math

@@ -5,6 +5,7 @@ Bar: every output equals tests/f32_oracle.py bit for bit (compared as uint32), i
 profiles, with a gray and with a 3-channel guide, and under both kernel selections: the
 radius-specialised vip::joint_f32_kernel (radius 1..15) and the runtime-radius
 vip::joint_f32_rt_kernel (radius 0 and 16..23, or every radius under VIP_PATH_RUNTIME).
+Frames of more tiles than the device has CUs (joint_f32_kernel's later rounds): tests/test_gpu_c1_rounds.py.
 """
 import functools
 

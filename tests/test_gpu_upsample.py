@@ -3,6 +3,7 @@ vip_upsample_run_f32).
 
 Bar: every output equals tests/upsample_oracle.py bit for bit (compared as uint32), in both
 numerics profiles, with a gray and with a 3-channel guide pair, at every scale.
+Frames of more tiles than the device has CUs (upsample_f32_kernel's later rounds): tests/test_gpu_c1_rounds.py.
 """
 import functools
 
