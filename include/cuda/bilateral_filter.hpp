@@ -60,6 +60,15 @@ public:
                                          const float hole_value, float* const d_dst, float* const d_weight,
                                          void* stream) const;
 
+    // The f32 form on an interleaved source of 1..4 channels (include/vip.h
+    // vip_joint_bilateral_run_f32c): d_src and d_dst are dense width x height x channels floats,
+    // every channel filtered under the same guide in one launch. ksize <= 47 / 31 / 15 / 15 for
+    // 1 / 2 / 3 / 4 channels. Blocking, and with a stream non-blocking.
+    void joint_bilateral_filter_f32c(const float* const d_src, const int channels, const std::uint8_t* const d_guide,
+                                     const int guide_channels, float* const d_dst) const;
+    void joint_bilateral_filter_f32c(const float* const d_src, const int channels, const std::uint8_t* const d_guide,
+                                     const int guide_channels, float* const d_dst, void* stream) const;
+
 protected:
     class Impl;  // defined in bilateral_filter_impl.cuh (test drivers reach it through impl_)
     std::unique_ptr<Impl> impl_;

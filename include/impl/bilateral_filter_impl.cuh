@@ -43,6 +43,9 @@ public:
                                          const std::uint8_t* const d_guide, const int guide_channels,
                                          const float hole_value, float* const d_dst, float* const d_weight,
                                          void* stream) const;
+    // the f32 form on 1..4 interleaved channels (stream-ordered; the class's blocking overload synchronises)
+    void joint_bilateral_filter_f32c(const float* const d_src, const int channels, const std::uint8_t* const d_guide,
+                                     const int guide_channels, float* const d_dst, void* stream) const;
 
     vip_bilateral_t handle() const { return handle_; }
 

@@ -73,14 +73,20 @@ int vip_max_radius(void);
  * sigma_space > 0); the texture filter any ksize from 1. The C++ and Python layers take
  * the same sets. Joint bilateral upsampling (no reference counterpart) takes odd ksize 1..9,
  * in low-resolution pixels; the confidence-weighted f32 joint bilateral (VIP_FILTER_JOINT_CONF) odd
- * ksize 1..31. Returns VIP_ERR_INVALID_ARGUMENT for an unknown filter. */
+ * ksize 1..31; the f32 joint bilateral on 2..4 interleaved channels (VIP_FILTER_JOINT_F32C) an odd
+ * ksize up to a cap that depends on the channel count: vip_max_ksize gives the largest, 31 (two
+ * channels), vip_joint_f32c_max_ksize(channels) each: 1: 47 (the f32 joint filter itself), 2: 31,
+ * 3: 15, 4: 15, VIP_ERR_INVALID_ARGUMENT otherwise.
+ * Returns VIP_ERR_INVALID_ARGUMENT for an unknown filter. */
 #define VIP_FILTER_BILATERAL 0
 #define VIP_FILTER_JOINT 1
 #define VIP_FILTER_ADAPTIVE 2
 #define VIP_FILTER_TEXTURE 3
 #define VIP_FILTER_UPSAMPLE 4
 #define VIP_FILTER_JOINT_CONF 5
+#define VIP_FILTER_JOINT_F32C 6
 int vip_max_ksize(int filter);
+int vip_joint_f32c_max_ksize(int channels);
 
 /* Kernel selection, process-wide (no reference counterpart; results are identical either
  * way). AUTO: radius-specialised kernels for radius 1..15, the runtime-radius kernel for
@@ -272,6 +278,47 @@ int vip_joint_bilateral_run_conf_f32(vip_bilateral_t h, const float* d_src, size
                                      size_t conf_pitch, const uint8_t* d_guide, size_t guide_pitch,
                                      int guide_channels, float hole_value, float* d_dst, size_t dst_pitch,
                                      float* d_weight /* may be NULL */, size_t weight_pitch, void* stream);
+/* ---- joint bilateral of an interleaved f32 source of 1..4 channels under an 8-bit guide (no
+ * counterpart in the reference's API): optical flow (2 channels), normals or float colour (3),
+ * RGBA, premultiplied colour or a small cost slice (4), every channel smoothed under the same
+ * guide in one launch. In a joint filter the weights come from the guide alone, so they are
+ * formed once per tap and serve every channel.
+ * d_src and d_dst are interleaved: channel c of pixel (x, y) is
+ *   ((float*)(base + y * pitch))[x * channels + c]
+ * The handle, ws, wc, the replicate border, d, the row-major tap order over the k x k square and
+ * the two numerics profiles are those of vip_joint_bilateral_run_f32. Per output pixel and tap:
+ *   w    = ws[ky,kx] * wc[d]            formed once
+ *   s_c  = fmaf(f_c(n), w, s_c)         for each channel c, VIP_NUMERICS_CUDA
+ *   s_c  = s_c + f_c(n) * w             for each channel c, VIP_NUMERICS_CPP (two roundings)
+ *   sumk = sumk + w                     once
+ *   dst_c = s_c / sumk                  IEEE binary32 division, no rounding to integer, no clamp
+ * Arithmetic is binary32 with gradual underflow (denormal mode 3, as the sibling kernels).
+ * Domain: every source value must be finite.
+ * Tie that holds bit for bit: for every c, plane c of dst is what vip_joint_bilateral_run_f32
+ * writes for plane c of src, in both profiles and with both guides, signed zeros and subnormals
+ * included. With an Inf or NaN in the source the values are unspecified, but the call cannot
+ * fault: every address comes from coordinates and the guide.
+ * channels 1 forwards to vip_joint_bilateral_run_f32 (the same kernels, the same ksize cap of 47,
+ * the same checks), so a caller generic over the channel count needs no branch. channels 2 takes
+ * odd ksize 1..31, channels 3 and 4 odd ksize 1..15 (vip_joint_f32c_max_ksize); a handle above
+ * the cap gives VIP_ERR_UNSUPPORTED_KSIZE. The caps: the filter keeps channels + 1 LDS planes
+ * (guide word, f_0 ..) where the f32 filter keeps two, and there is no runtime-radius kernel for
+ * channels >= 2; vip_set_stencil_path and the vip_bilateral_set_* knobs do not apply.
+ * Pitches are in bytes. The float bases and pitches must be multiples of 4; 16-byte accesses are
+ * used only where base and pitch are multiples of 16, decided separately for d_src and d_dst.
+ * d_guide may have any base and pitch. No byte of d_dst is written at a byte offset
+ * >= width * channels * 4 within a row, nor at a row >= height.
+ * VIP_ERR_INVALID_ARGUMENT: a null handle or pointer; channels outside 1..4; guide_channels not 1
+ * or 3; a misaligned float base or pitch; a pitch smaller than a row. VIP_ERR_ALIASING: d_dst
+ * equals d_src or d_guide. One launch per call, asynchronous, no device allocation:
+ * vip::joint_f32c_kernel<R, C, GUIDE, FMA> for radius 1..15 (C = 2) or 1..7 (C = 3, 4),
+ * vip::joint_f32c_k1_kernel<C, FMA> for ksize 1 (dst_c = fmaf(f_c, w, 0) / (0 + w) with
+ * w = ws[0] * wc[0]; the guide is not read); the launch log and vip_kernel_timing_* see them.
+ * Against C launches of vip_joint_bilateral_run_f32 on de-interleaved planes: see DESIGN.md
+ * section 4 for the measured times; nothing here promises a speed. */
+int vip_joint_bilateral_run_f32c(vip_bilateral_t h, const float* d_src, size_t src_pitch, int channels,
+                                 const uint8_t* d_guide, size_t guide_pitch, int guide_channels, float* d_dst,
+                                 size_t dst_pitch, void* stream);
 /* ---- joint bilateral upsampling (Kopf et al. 2007; no counterpart in the reference's API): a
  * field f solved at 1/2, 1/4 or 1/8 scale is brought up to the frame under the full-resolution
  * image, in one launch, with no full-resolution float intermediate.

@@ -11,6 +11,7 @@ from ._lib import (  # noqa: F401
     VIP_FILTER_BILATERAL,
     VIP_FILTER_JOINT,
     VIP_FILTER_JOINT_CONF,
+    VIP_FILTER_JOINT_F32C,
     VIP_FILTER_TEXTURE,
     VIP_FILTER_UPSAMPLE,
     VIP_PATH_AUTO,

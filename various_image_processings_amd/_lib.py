@@ -22,6 +22,7 @@ VIP_ERR_ALIASING = 10003
 VIP_FILTER_BILATERAL, VIP_FILTER_JOINT, VIP_FILTER_ADAPTIVE, VIP_FILTER_TEXTURE = 0, 1, 2, 3
 VIP_FILTER_UPSAMPLE = 4
 VIP_FILTER_JOINT_CONF = 5
+VIP_FILTER_JOINT_F32C = 6
 VIP_PATH_AUTO, VIP_PATH_RUNTIME = 0, 1
 
 _c_void_p = ctypes.c_void_p
@@ -86,6 +87,10 @@ SIGNATURES = {
     "vip_joint_bilateral_run_conf_f32": (
         _c_int, [_c_void_p, _c_void_p, _c_size_t, _c_void_p, _c_size_t, _c_void_p, _c_size_t, _c_int, _c_float,
                  _c_void_p, _c_size_t, _c_void_p, _c_size_t, _c_void_p]),
+    "vip_joint_bilateral_run_f32c": (
+        _c_int, [_c_void_p, _c_void_p, _c_size_t, _c_int, _c_void_p, _c_size_t, _c_int, _c_void_p, _c_size_t,
+                 _c_void_p]),
+    "vip_joint_f32c_max_ksize": (_c_int, [_c_int]),
     "vip_upsample_create": (
         _c_int, [ctypes.POINTER(_c_void_p), _c_int, _c_int, _c_int, _c_int, _c_float, _c_float, _c_int]),
     "vip_upsample_destroy": (_c_int, [_c_void_p]),

@@ -98,6 +98,9 @@ constexpr int kMaxKsizeBilateral = 65, kMaxKsizeJoint = 47, kMaxKsizeAdaptive = 
 constexpr int kMaxKsizeUpsample = 2 * kUpMaxRadius + 1;
 // the confidence-weighted f32 joint filter has the radius-specialised kernels only (three LDS planes)
 constexpr int kMaxKsizeJointConf = 2 * kMaxRadius + 1;
+// the multi-channel f32 joint filter likewise (C + 1 LDS planes): by channel count, index 0 unused;
+// one channel is the f32 joint filter itself
+constexpr int kMaxKsizeJointF32c[5] = {0, kMaxKsizeJoint, 31, 15, 15};
 static bool valid_ksize(int ksize, int max_ksize) { return ksize >= 1 && (ksize & 1) && ksize <= max_ksize; }
 
 // vip_set_stencil_path: VIP_PATH_AUTO (templated kernels for radius 1..15, the
@@ -487,8 +490,13 @@ int vip_max_ksize(int filter) {
         case VIP_FILTER_TEXTURE: return kMaxKsizeTexture;
         case VIP_FILTER_UPSAMPLE: return kMaxKsizeUpsample;
         case VIP_FILTER_JOINT_CONF: return kMaxKsizeJointConf;
+        case VIP_FILTER_JOINT_F32C: return kMaxKsizeJointF32c[2];
         default: return VIP_ERR_INVALID_ARGUMENT;
     }
+}
+
+int vip_joint_f32c_max_ksize(int channels) {
+    return channels >= 1 && channels <= 4 ? kMaxKsizeJointF32c[channels] : VIP_ERR_INVALID_ARGUMENT;
 }
 
 int vip_set_stencil_path(int path) {
@@ -521,7 +529,7 @@ const char* vip_error_string(int code) {
         case VIP_ERR_INVALID_ARGUMENT: return "invalid argument";
         case VIP_ERR_UNSUPPORTED_KSIZE:
             return "unsupported ksize (odd, 1..65 bilateral, 1..47 joint bilateral, 1..63 adaptive, 1..9 upsampling, 1..31 confidence-weighted "
-                   "joint; texture 1..24)";
+                   "joint, 1..31 / 1..15 joint on 2 / 3-4 f32 channels; texture 1..24)";
         case VIP_ERR_ALIASING: return "source and destination alias";
         default: return hipGetErrorString((hipError_t)code);
     }
@@ -711,6 +719,34 @@ int vip_joint_bilateral_run_conf_f32(vip_bilateral_t h, const float* d_src, size
     a.weight_aligned = d_weight && is_aligned(d_weight, weight_pitch, 16);
     a.hole_value = hole_value;
     return launch_joint_conf_f32(h->radius, guide_channels, h->numerics == VIP_NUMERICS_CUDA, a, (hipStream_t)stream);
+}
+
+// ---- the f32 joint filter on an interleaved source of 2..4 channels (vip_joint_f32c.hip): the whole
+// frame, the radius-specialised kernels only; a row is width * channels floats, and the 16-byte
+// accesses are decided for src and dst each on its own
+int vip_joint_bilateral_run_f32c(vip_bilateral_t h, const float* d_src, size_t src_pitch, int channels,
+                                 const uint8_t* d_guide, size_t guide_pitch, int guide_channels, float* d_dst,
+                                 size_t dst_pitch, void* stream) {
+    if (!h || !d_src || !d_guide || !d_dst) return VIP_ERR_INVALID_ARGUMENT;
+    if (channels < 1 || channels > 4) return VIP_ERR_INVALID_ARGUMENT;
+    if (channels == 1)
+        return vip_joint_bilateral_run_f32(h, d_src, src_pitch, d_guide, guide_pitch, guide_channels, d_dst, dst_pitch,
+                                           stream);
+    if (guide_channels != 1 && guide_channels != 3) return VIP_ERR_INVALID_ARGUMENT;
+    if (!is_aligned(d_src, src_pitch, 4) || !is_aligned(d_dst, dst_pitch, 4)) return VIP_ERR_INVALID_ARGUMENT;
+    const size_t frow = sizeof(float) * (size_t)channels * (size_t)h->width;
+    if (src_pitch < frow || dst_pitch < frow || guide_pitch < (size_t)guide_channels * (size_t)h->width)
+        return VIP_ERR_INVALID_ARGUMENT;
+    if (d_dst == d_src || (const void*)d_dst == (const void*)d_guide) return VIP_ERR_ALIASING;
+    if (h->ksize > kMaxKsizeJointF32c[channels]) return VIP_ERR_UNSUPPORTED_KSIZE;
+    const RowBand b{reinterpret_cast<const uint8_t*>(d_src), src_pitch, d_guide, guide_pitch,
+                    reinterpret_cast<uint8_t*>(d_dst), dst_pitch, h->height, 0, 0, h->height};
+    StencilArgs a = stencil_args(*h, b);
+    a.aligned = (is_aligned(d_guide, guide_pitch, 4) ? kF32GuideWords : 0) |
+                (is_aligned(d_src, src_pitch, 16) ? kF32SrcVec : 0);
+    a.dst_aligned = is_aligned(d_dst, dst_pitch, 16);
+    const bool fma = h->numerics == VIP_NUMERICS_CUDA;
+    return launch_joint_f32c(h->radius, channels, guide_channels, fma, a, (hipStream_t)stream);
 }
 
 // ---- joint bilateral upsampling (vip_upsample.hip): a handle of its own, since the spatial

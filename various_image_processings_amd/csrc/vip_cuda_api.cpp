@@ -102,6 +102,14 @@ void CudaBilateralFilter::Impl::joint_bilateral_filter_conf_f32(const float* con
                                                 pitch * (size_t)(guide_channels == 3 ? 3 : 1), guide_channels,
                                                 hole_value, d_dst, fp, d_weight, fp, stream));
 }
+void CudaBilateralFilter::Impl::joint_bilateral_filter_f32c(const float* const d_src, const int channels,
+                                                            const std::uint8_t* const d_guide, const int guide_channels,
+                                                            float* const d_dst, void* stream) const {
+    const size_t pitch = (size_t)width_, fp = pitch * sizeof(float) * (size_t)(channels > 0 ? channels : 0);
+    VIP_REPORT(vip_joint_bilateral_run_f32c(handle_, d_src, fp, channels, d_guide,
+                                            pitch * (size_t)(guide_channels == 3 ? 3 : 1), guide_channels, d_dst, fp,
+                                            stream));
+}
 
 CudaBilateralFilter::CudaBilateralFilter(const int width, const int height, const int ksize, const float sigma_space,
                                          const float sigma_color)
@@ -171,6 +179,17 @@ void CudaBilateralFilter::joint_bilateral_filter_conf_f32(const float* const d_s
                                                           float* const d_weight, void* stream) const {
     impl_->joint_bilateral_filter_conf_f32(d_src, d_conf, d_guide, guide_channels, hole_value, d_dst, d_weight,
                                            stream);
+}
+void CudaBilateralFilter::joint_bilateral_filter_f32c(const float* const d_src, const int channels,
+                                                      const std::uint8_t* const d_guide, const int guide_channels,
+                                                      float* const d_dst) const {
+    impl_->joint_bilateral_filter_f32c(d_src, channels, d_guide, guide_channels, d_dst, nullptr);
+    VIP_REPORT(vip_device_synchronize());
+}
+void CudaBilateralFilter::joint_bilateral_filter_f32c(const float* const d_src, const int channels,
+                                                      const std::uint8_t* const d_guide, const int guide_channels,
+                                                      float* const d_dst, void* stream) const {
+    impl_->joint_bilateral_filter_f32c(d_src, channels, d_guide, guide_channels, d_dst, stream);
 }
 
 // ------------------------------------------------------------ CudaJointBilateralUpsample

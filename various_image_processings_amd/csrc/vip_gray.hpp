@@ -29,6 +29,29 @@ struct GrayWord {
 constexpr int kGrayCopies = 32;
 static_assert(kGrayCopies * 4 == 1 << GrayWord<0>::LUT_SHIFT, "LUT address: d << 7");
 
+// LutStage for 8 copies (LutStage takes 16 or 32): word d * 8 + c = color[d], two uint4 stores per
+// entry (vip_joint_conf.hip and vip_joint_f32c.hip, where 16 copies leave LDS for 4 waves only)
+template <int NT, int ENTRIES>
+struct LutStage8 {
+    static constexpr int N = ENTRIES * 2;  // uint4 stores
+    static constexpr int K = (N + NT - 1) / NT;
+    uint32_t v[K];
+    __device__ __forceinline__ void load(const float* color) {
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            const int q = (int)threadIdx.x + k * NT;
+            if (N % NT == 0 || q < N) v[k] = __float_as_uint(color[q >> 1]);
+        }
+    }
+    __device__ __forceinline__ void store(uint32_t* lut) const {
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            const int q = (int)threadIdx.x + k * NT;
+            if (N % NT == 0 || q < N) *reinterpret_cast<uint4*>(lut + 4 * q) = make_uint4(v[k], v[k], v[k], v[k]);
+        }
+    }
+};
+
 // 4 gray pixels of one image row from column x (columns clamped to the image), pixel k in
 // byte k: one dword load when the group is interior and the row is dword aligned.
 __device__ __forceinline__ uint32_t load_gray4(const uint8_t* row, int x, int width, int aligned) {

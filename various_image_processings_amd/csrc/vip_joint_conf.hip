@@ -67,28 +67,6 @@ struct ConfGuide {
     static constexpr int LUTW = ENTRIES * COPIES;
 };
 
-// LutStage for 8 copies (LutStage takes 16 or 32): word d * 8 + c = color[d], two uint4 stores per entry
-template <int NT, int ENTRIES>
-struct LutStage8 {
-    static constexpr int N = ENTRIES * 2;  // uint4 stores
-    static constexpr int K = (N + NT - 1) / NT;
-    uint32_t v[K];
-    __device__ __forceinline__ void load(const float* color) {
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-            const int q = (int)threadIdx.x + k * NT;
-            if (N % NT == 0 || q < N) v[k] = __float_as_uint(color[q >> 1]);
-        }
-    }
-    __device__ __forceinline__ void store(uint32_t* lut) const {
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-            const int q = (int)threadIdx.x + k * NT;
-            if (N % NT == 0 || q < N) *reinterpret_cast<uint4*>(lut + 4 * q) = make_uint4(v[k], v[k], v[k], v[k]);
-        }
-    }
-};
-
 // Waves per workgroup: the most whose three planes fit LDS, and fewer from the radius on at which
 // that workgroup's registers (16 waves: 128 VGPRs, 12: 168, 8: 256) no longer hold the kernel
 // without scratch: with a gray guide 16 waves spill at R = 4 and 12 waves at R = 10, 11; with a

@@ -145,6 +145,10 @@ struct ConfArgs : StencilArgs {
     int weight_aligned;    // weight base and pitch are 16-byte aligned -> float4 stores
 };
 int launch_joint_conf_f32(int radius, int guide_channels, bool fma, const ConfArgs& a, hipStream_t s);
+// vip_joint_f32c.hip: launch_joint_f32's filter on an interleaved f32 source of channels = 2..4
+// (radius 0..15 at C = 2, 0..7 at C = 3 and 4, VIP_ERR_UNSUPPORTED_KSIZE beyond; no runtime-radius
+// kernel). StencilArgs exactly as launch_joint_f32 reads it: a pixel of src and dst is C floats.
+int launch_joint_f32c(int radius, int channels, int guide_channels, bool fma, const StencilArgs& a, hipStream_t s);
 int launch_gradient_u8(const uint8_t* src, float* dst, int width, int height, int ch, hipStream_t stream);
 int launch_gradient_f32(const float* src, float* dst, int width, int height, int ch, bool fma, hipStream_t stream);
 int launch_blur_rtv(const uint8_t* img, const float* mag, float* blurred, float* rtv, int width, int height,

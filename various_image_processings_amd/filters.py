@@ -10,7 +10,9 @@ yuyuyu-bot/various_image_processings:
   and ``joint_bilateral_filter_f32(d_src, d_guide, guide_channels, d_dst)``: a float32 one-channel source
   and destination under an 8-bit guide (no reference counterpart), and its confidence-weighted form
   ``joint_bilateral_filter_conf_f32(d_src, d_conf, d_guide, guide_channels, d_dst, hole_value=0.,
-  d_weight=None)``, which fills holes (ksize <= 31)
+  d_weight=None)``, which fills holes (ksize <= 31), and its multi-channel form
+  ``joint_bilateral_filter_f32c(d_src, channels, d_guide, guide_channels, d_dst)`` on an interleaved float32
+  source of 1..4 channels (ksize <= 47 / 31 / 15 / 15)
 * ``CudaAdaptiveBilateralFilter(...).execute(d_src, d_dst)`` (adaptive_bilateral_filter.hpp:9-19), and its
   one-channel form ``execute_c1(d_src, d_dst)`` (no reference counterpart)
 * ``CudaBilateralTextureFilter(width, height, ksize=9, nitr=3).execute(d_src, d_dst)``
@@ -101,7 +103,8 @@ def set_stencil_path(path: int = _lib.VIP_PATH_AUTO) -> None:
 def max_ksize(filter_kind: int) -> int:
     """Largest ksize a filter accepts (include/vip.h vip_max_ksize): what the reference
     runs -- bilateral 65, joint 47, adaptive 63, texture 24 -- and 9 for joint bilateral upsampling, 31 for the
-    confidence-weighted f32 joint filter."""
+    confidence-weighted f32 joint filter and for the f32 joint filter on two interleaved channels
+    (VIP_FILTER_JOINT_F32C; 15 on three or four: vip_joint_f32c_max_ksize)."""
     return int(lib().vip_max_ksize(int(filter_kind)))
 
 
@@ -268,6 +271,19 @@ class _BilateralImpl(_Handle):
              _ptr(d_conf, 4 * n, dtype="float32"), 4 * p, _ptr(d_guide, n * gch), p * gch, gch, float(hole_value),
              _ptr(d_dst, 4 * n, dtype="float32"), 4 * p, wgt, 4 * p, _stream(stream))
 
+    def joint_bilateral_filter_f32c(self, d_src, channels, d_guide, guide_channels, d_dst, stream=None):
+        """The f32 form on an interleaved source of 1..4 channels (include/vip.h
+        vip_joint_bilateral_run_f32c): d_src and d_dst are width * height * channels float32, every
+        channel filtered under the same guide in one launch."""
+        gch = self._guide_channels(guide_channels, "vip_joint_bilateral_run_f32c")
+        ch = int(channels)
+        if not 1 <= ch <= 4:
+            raise VipError("vip_joint_bilateral_run_f32c", _lib.VIP_ERR_INVALID_ARGUMENT)
+        p, n = self.width, self.width * self.height
+        call("vip_joint_bilateral_run_f32c", self._h, _ptr(d_src, 4 * n * ch, dtype="float32"), 4 * p * ch, ch,
+             _ptr(d_guide, n * gch), p * gch, gch, _ptr(d_dst, 4 * n * ch, dtype="float32"), 4 * p * ch,
+             _stream(stream))
+
     def run_rows_batch(self, d_srcs, d_dsts, out_rows, src_row0, row_lo, row_hi, free_cus=0, stream=None):
         """run_rows over several frames of the same geometry, up to 6 per launch
         (include/vip.h vip_bilateral_run_rows_batch)."""
@@ -318,6 +334,11 @@ class CudaBilateralFilter:
         """Confidence-weighted f32 form, which fills holes (include/vip.h vip_joint_bilateral_run_conf_f32)."""
         self.impl_.joint_bilateral_filter_conf_f32(d_src, d_conf, d_guide, guide_channels, d_dst, hole_value,
                                                    d_weight)
+        device_synchronize()
+
+    def joint_bilateral_filter_f32c(self, d_src, channels, d_guide, guide_channels, d_dst):
+        """The f32 form on an interleaved source of 1..4 channels (include/vip.h vip_joint_bilateral_run_f32c)."""
+        self.impl_.joint_bilateral_filter_f32c(d_src, channels, d_guide, guide_channels, d_dst)
         device_synchronize()
 
 
