@@ -4,8 +4,11 @@ Parity status: pinned where the reference ships an executable oracle. The REF
 profile equals the reference tests' own CPU oracles (test/adaptive_bilateral_filter.cu,
 test/bilateral_texture_filter.cu, test/gradient.cu Ref* code, compiled in place by
 oracle/Makefile) bit for bit on tests/golden/ref_oracles.npz: adaptive, gradient,
-blur/mRTV and guide are pinned. Bilateral / joint bilateral stay "parity unpinned":
-their only reference oracle is cv::bilateralFilter (OpenCV, absent here). The
+blur/mRTV and guide are pinned. The CPP profile of bilateral, joint bilateral and
+adaptive equals the reference's include/cpp filters, compiled whole over our own
+stand-in for OpenCV's containers, bit for bit on tests/golden/ref_cpp_filters.npz
+(whole frames). Unpinned: the CUDA profile's fma contraction and the whole-pipeline
+texture filter (include/cpp calls cv::ximgproc); nothing here can execute them. The
 mt19937 input generator is pinned to test/random_array.hpp (tests/golden).
 Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline may use this.
 """

@@ -1,9 +1,12 @@
 """TEST INFRASTRUCTURE ONLY: ctypes wrapper of oracle/_ref/libref_test_oracles.so, the
 reference tests' own CPU oracles compiled where they lie (oracle/ref_test_oracles.cpp,
-oracle/Makefile). Exists only in the dev container, where /root/reference is mounted:
-tests/golden/make_ref_golden.py turns its outputs into the committed fixture
-tests/golden/ref_oracles.npz, and tests/test_ref_pinned.py re-derives that fixture live
-when the library is present. Nothing on the GPU box loads it."""
+oracle/Makefile), and of oracle/_ref/libref_cpp_filters.so, the reference's include/cpp
+CPU filters compiled whole over our stand-in for OpenCV's containers
+(oracle/ref_cpp_filters.cpp, oracle/cv_standin/). Exists only in the dev container, where
+the reference is mounted: tests/golden/make_ref_golden.py turns its outputs into the
+committed fixtures tests/golden/ref_oracles.npz and ref_cpp_filters.npz, and
+tests/test_ref_pinned.py re-derives those fixtures live when the libraries are present.
+Nothing on the GPU box loads it."""
 from __future__ import annotations
 
 import ctypes
@@ -13,11 +16,13 @@ import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "_ref", "libref_test_oracles.so")
+CPP_LIB_PATH = os.path.join(HERE, "_ref", "libref_cpp_filters.so")
 _lib = None
+_cpp_lib = None
 
 
 def available() -> bool:
-    return os.path.exists(LIB_PATH)
+    return os.path.exists(LIB_PATH) and os.path.exists(CPP_LIB_PATH)
 
 
 def lib() -> ctypes.CDLL:
@@ -35,6 +40,20 @@ def lib() -> ctypes.CDLL:
             getattr(L, fn).restype = None
         _lib = L
     return _lib
+
+
+def cpp_lib() -> ctypes.CDLL:
+    global _cpp_lib
+    if _cpp_lib is None:
+        L = ctypes.CDLL(CPP_LIB_PATH)
+        vp, i, f = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
+        L.ref_cpp_bilateral.argtypes = [vp, vp, i, i, i, f, f]
+        L.ref_cpp_joint.argtypes = [vp, vp, vp, i, i, i, f, f]
+        L.ref_cpp_adaptive.argtypes = [vp, vp, i, i, i, f, f]
+        for fn in ("ref_cpp_bilateral", "ref_cpp_joint", "ref_cpp_adaptive"):
+            getattr(L, fn).restype = None
+        _cpp_lib = L
+    return _cpp_lib
 
 
 def _c(a, dt):
@@ -87,3 +106,31 @@ def cpp_luts(ksize, sigma_space, sigma_color, color_len=768):
     color = np.empty(color_len, np.float32)
     lib().ref_cpp_luts(ksize, sigma_space, sigma_color, color_len, space.ctypes.data, color.ctypes.data)
     return space, color
+
+
+def cpp_bilateral(src, ksize=9, sigma_space=10.0, sigma_color=30.0):
+    """bilateral_filter (include/cpp/bilateral_filter.hpp), whole frame."""
+    src = _c(src, np.uint8)
+    h, w, _ = src.shape
+    dst = np.empty_like(src)
+    cpp_lib().ref_cpp_bilateral(src.ctypes.data, dst.ctypes.data, w, h, ksize, sigma_space, sigma_color)
+    return dst
+
+
+def cpp_joint(src, guide, ksize=9, sigma_space=10.0, sigma_color=30.0):
+    """joint_bilateral_filter (include/cpp/bilateral_filter.hpp): src filtered under guide."""
+    src, guide = _c(src, np.uint8), _c(guide, np.uint8)
+    assert src.shape == guide.shape
+    h, w, _ = src.shape
+    dst = np.empty_like(src)
+    cpp_lib().ref_cpp_joint(src.ctypes.data, guide.ctypes.data, dst.ctypes.data, w, h, ksize, sigma_space, sigma_color)
+    return dst
+
+
+def cpp_adaptive(src, ksize=9, sigma_space=10.0, sigma_color=30.0):
+    """adaptive_bilateral_filter (include/cpp/adaptive_bilateral_filter.hpp)."""
+    src = _c(src, np.uint8)
+    h, w, _ = src.shape
+    dst = np.empty_like(src)
+    cpp_lib().ref_cpp_adaptive(src.ctypes.data, dst.ctypes.data, w, h, ksize, sigma_space, sigma_color)
+    return dst

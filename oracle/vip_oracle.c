@@ -7,13 +7,16 @@
  * checker / CPU baseline. The product path (various_image_processings_amd/)
  * never links or calls it.
  *
- * Parity status: the reference is unbuildable in this image (include/cpp needs
- * OpenCV core + ximgproc, src/ needs nvcc + thrust, test/ needs gtest), so
- * this restatement is "parity unpinned" against reference *execution*. What is
- * pinned: the input generator below is checked bit-for-bit against the
- * reference's own test/random_array.hpp compiled in place (oracle/Makefile,
- * tests/golden/random_array_*.bin). Every function cites the reference lines it
- * restates.
+ * Parity status: the reference as a whole is unbuildable in this image (include/cpp
+ * needs OpenCV core + ximgproc, src/ needs nvcc + thrust, test/ needs gtest). What is
+ * pinned to reference *execution*: the input generator below, bit for bit against
+ * test/random_array.hpp compiled in place (oracle/Makefile,
+ * tests/golden/random_array_*.bin); the REF profile against the reference tests' own
+ * CPU oracles (below); and the CPP profile of bilateral, joint bilateral and adaptive
+ * against the include/cpp filters compiled whole over our own stand-in for OpenCV's
+ * containers (oracle/ref_cpp_filters.cpp, tests/golden/ref_cpp_filters.npz). Unpinned:
+ * the CUDA profile's fma contraction and the whole-pipeline texture filter. Every
+ * function cites the reference lines it restates.
  *
  * Two numerics profiles, because the reference's own CPU and GPU paths differ:
  *   VIPO_CUDA (0): src/<filter>_impl.cu — float-coefficient LUTs built with expf on the

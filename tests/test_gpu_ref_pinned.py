@@ -10,6 +10,22 @@ reference's own CUDA tests apply to its kernels:
 
 Frames beyond the fixture's 50x50 arrays (640x360, lenna) compare with the oracle's REF
 profile, which tests/test_ref_pinned.py pins to those Ref oracles by sha256.
+
+And against the reference's include/cpp CPU filters (tests/golden/ref_cpp_filters.npz:
+bilateral_filter, joint_bilateral_filter, adaptive_bilateral_filter compiled whole where they
+lie over our own stand-in for OpenCV's containers -- the reference's arithmetic text ran,
+OpenCV's containers did not), on whole frames, borders included, with a guide distinct from
+the source:
+
+  VIP_NUMERICS_CPP    equal, bit for bit (include/cpp defines that profile)
+  VIP_NUMERICS_CUDA   +-1 per channel (test/bilateral_filter.cu EXPECT_NEAR 1; exact share printed)
+
+The 50x50 outputs are stored whole. The tile-crossing frame, 640x360 and lenna compare with
+the oracle's CPP profile, which tests/test_ref_pinned.py pins to include/cpp by sha256. The
+f32 multi-channel joint filter on float32(src), rounded, is tied to the same joint entries.
+Nothing here reads oracle/_ref/ or the reference. Still unpinned, because nothing here can
+execute it: the CUDA profile's fma contraction, and the whole-pipeline texture filter, whose
+include/cpp form calls cv::ximgproc.
 """
 import os
 import sys
@@ -113,3 +129,97 @@ def test_gradient_vs_reference_oracle(dev, fixture, inputs, name, numerics):
     d_dst = dev.empty((50, 50), np.float32)
     vip.cuda_gradient(dev.put(src), d_dst, 50, 50, src.shape[2], numerics=numerics)
     assert ulps(dev.get(d_dst), fixture[f"gradient_{name}"]).max() <= 4
+
+
+# ---- include/cpp filters: tests/golden/ref_cpp_filters.npz ----
+@pytest.fixture(scope="module")
+def cppfix():
+    return dict(np.load(os.path.join(GOLDEN, "ref_cpp_filters.npz")))
+
+
+@pytest.fixture(scope="module")
+def cpp_inputs(oracle, lenna):
+    return mrg.cpp_inputs(oracle, lenna)
+
+
+@pytest.fixture(scope="module")
+def cpp_large(oracle, cpp_inputs):
+    """The oracle's CPP profile on the digest cases, once for both numerics."""
+    f = mrg.oracle_filters(oracle, oracle.CPP, threads=16)
+    out = {(name, k): mrg.cpp_frame(f, cpp_inputs, name, k) for name, k in (("tile", 9), ("f640", 15))}
+    out[("lenna", 11)] = dict(bilateral=f["bilateral"](cpp_inputs["lenna"][0], 11, 10.0, 30.0))
+    return out
+
+
+def _bilateral(dev, img, k, ss, sc, numerics, guide=None):
+    h, w, _ = img.shape
+    f = vip.CudaBilateralFilter(w, h, k, ss, sc, numerics=numerics)
+    d_dst = dev.empty((h, w, 3))
+    if guide is None:
+        f.bilateral_filter(dev.put(img), d_dst)
+    else:
+        f.joint_bilateral_filter(dev.put(img), dev.put(guide), d_dst)
+    return dev.get(d_dst)
+
+
+def _cpp_check(got, want, numerics, what):
+    """CPP numerics: the include/cpp bytes. CUDA numerics: the reference tests' +-1."""
+    if numerics == vip.VIP_NUMERICS_CPP:
+        bad = np.argwhere(got != want)
+        assert len(bad) == 0, (what, len(bad), bad[:5].tolist())
+    else:
+        _near1(got, want, what + " CUDA numerics")
+
+
+@pytest.mark.parametrize("numerics", NUMERICS)
+@pytest.mark.parametrize("k,ss,sc", mrg.CPP_BILATERAL)
+def test_bilateral_vs_include_cpp(dev, cppfix, cpp_inputs, k, ss, sc, numerics):
+    got = _bilateral(dev, cpp_inputs["f50"][0], k, ss, sc, numerics)
+    _cpp_check(got, cppfix[mrg.bil_key(k, ss, sc)], numerics, mrg.bil_key(k, ss, sc))
+
+
+@pytest.mark.parametrize("numerics", NUMERICS)
+@pytest.mark.parametrize("k", mrg.CPP_JOINT_K)
+def test_joint_bilateral_vs_include_cpp(dev, cppfix, cpp_inputs, k, numerics):
+    img, guide = cpp_inputs["f50"]
+    got = _bilateral(dev, img, k, 10.0, 30.0, numerics, guide=guide)
+    _cpp_check(got, cppfix[f"cpp_joint_k{k}"], numerics, f"cpp_joint_k{k}")
+
+
+@pytest.mark.parametrize("numerics", NUMERICS)
+@pytest.mark.parametrize("k", mrg.CPP_ADAPTIVE_K)
+def test_adaptive_vs_include_cpp(dev, cppfix, cpp_inputs, k, numerics):
+    got = _adaptive(dev, cpp_inputs["f50"][0], k, numerics)
+    _cpp_check(got, cppfix[f"cpp_adaptive_k{k}"], numerics, f"cpp_adaptive_k{k}")
+
+
+@pytest.mark.parametrize("numerics", NUMERICS)
+@pytest.mark.parametrize("name,k", [("tile", 9), ("f640", 15), ("lenna", 11)])
+def test_filters_vs_include_cpp_large(dev, cppfix, cpp_inputs, cpp_large, name, k, numerics):
+    """The 259x70 frame (every tile of the 3-channel kernels crossed, ksize 9), 640x360 (ksize
+    15) and lenna (ksize 11, bilateral): the oracle's CPP profile carries the include/cpp
+    digest (asserted), and the HIP outputs compare with it."""
+    img, guide = cpp_inputs[name]
+    for flt, want in cpp_large[(name, k)].items():
+        assert np.array_equal(mrg.sha(want), cppfix[f"cpp_{flt}_{name}_k{k}_sha256"]), flt
+        if flt == "adaptive":
+            got = _adaptive(dev, img, k, numerics)
+        else:
+            got = _bilateral(dev, img, k, 10.0, 30.0, numerics, guide=guide if flt == "joint" else None)
+        _cpp_check(got, want, numerics, f"cpp_{flt}_{name}_k{k}")
+
+
+@pytest.mark.parametrize("numerics", NUMERICS)
+@pytest.mark.parametrize("k", [9, 15])
+def test_joint_f32c_rounded_vs_include_cpp(dev, cppfix, cpp_inputs, k, numerics):
+    """The f32 family tied to the same execution: joint_bilateral_filter_f32c on the three
+    channels of float32(src) under the 3-channel guide, rounded (uint8)(v + 0.5f) with the
+    addition in float32 and a truncating cast, against include/cpp's joint filter."""
+    img, guide = cpp_inputs["f50"]
+    h, w, _ = img.shape
+    d_dst = dev.empty((h, w, 3), np.float32)
+    f = vip.CudaBilateralFilter(w, h, k, numerics=numerics)
+    f.joint_bilateral_filter_f32c(dev.put(img.astype(np.float32)), 3, dev.put(guide), 3, d_dst)
+    v = (dev.get(d_dst) + np.float32(0.5)).astype(np.float32)
+    assert np.isfinite(v).all() and v.min() >= 0 and v.max() < 256
+    _cpp_check(v.astype(np.int32).astype(np.uint8), cppfix[f"cpp_joint_k{k}"], numerics, f"f32c rounded joint k{k}")
