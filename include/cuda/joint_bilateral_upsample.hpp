@@ -3,7 +3,9 @@
 // libvip_hip.so, gfx950 HIP kernels), which holds the definition.
 // Pointers are device pointers to dense images: d_src_lo low_width() x low_height() floats,
 // d_guide_lo the same size in bytes times guide_channels (1: gray, 3: interleaved), d_guide
-// width x height x guide_channels bytes, d_dst width x height floats. The call without a stream
+// width x height x guide_channels bytes, d_dst width x height floats; upsample_f32c takes
+// channels (1..4) interleaved floats per cell of d_src_lo and per pixel of d_dst
+// (vip_upsample_run_f32c: each channel is upsample_f32 on its plane). The call without a stream
 // blocks until the GPU is done, like the other classes' public calls; with a stream (a
 // hipStream_t passed as void*, nullptr = default stream) it enqueues and returns at once.
 #ifndef VIP_CUDA_JOINT_BILATERAL_UPSAMPLE_HPP
@@ -27,6 +29,11 @@ public:
     void upsample_f32(const float* const d_src_lo, const std::uint8_t* const d_guide_lo,
                       const std::uint8_t* const d_guide, const int guide_channels, float* const d_dst,
                       void* stream) const;
+    void upsample_f32c(const float* const d_src_lo, const int channels, const std::uint8_t* const d_guide_lo,
+                       const std::uint8_t* const d_guide, const int guide_channels, float* const d_dst) const;
+    void upsample_f32c(const float* const d_src_lo, const int channels, const std::uint8_t* const d_guide_lo,
+                       const std::uint8_t* const d_guide, const int guide_channels, float* const d_dst,
+                       void* stream) const;
 
     // ceil(width / scale), ceil(height / scale)
     int low_width() const { return low_width_; }

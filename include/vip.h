@@ -368,6 +368,40 @@ int vip_upsample_low_size(int width, int height, int scale, int* low_width, int*
 int vip_upsample_run_f32(vip_upsample_t h, const float* d_src_lo, size_t src_pitch, const uint8_t* d_guide_lo,
                          size_t guide_lo_pitch, const uint8_t* d_guide, size_t guide_pitch, int guide_channels,
                          float* d_dst, size_t dst_pitch, void* stream);
+/* ---- vip_upsample_run_f32 on an interleaved low-resolution field of 2..4 channels (flow at 1/4
+ * scale, normals, float colour, RGBA), in one launch on the same handle: the weights depend on the
+ * guides alone, so they are formed once per tap and serve every channel.
+ * d_src_lo is low_width x low_height x channels and d_dst width x height x channels, interleaved:
+ * channel c of cell or pixel (x, y) is
+ *   ((float*)(base + y * pitch))[x * channels + c]
+ * The handle, the guides, the scale, wsp, wc, d, the clamped cells and the row-major tap order are
+ * those of vip_upsample_run_f32. Per output pixel and tap:
+ *   wgt  = wsp * wc[d]                   formed once
+ *   s_c  = fmaf(f_c(ix,iy), wgt, s_c)    for each channel c, VIP_NUMERICS_CUDA
+ *   s_c  = s_c + f_c(ix,iy) * wgt        for each channel c, VIP_NUMERICS_CPP (two roundings)
+ *   sumk = sumk + wgt                    once
+ *   dst_c(x,y) = sumk == 0 ? f_c(cx, cy) : s_c / sumk
+ * Arithmetic is binary32 with gradual underflow (denormal mode 3, as the sibling kernels).
+ * Tie that holds bit for bit: for every c, plane c of dst is what vip_upsample_run_f32 writes for
+ * plane c of the source, in both profiles, with both guide forms and at every scale, signed
+ * zeros, subnormals and the sumk == 0 fallback included. With an Inf or NaN in the source the
+ * values are unspecified, but the call cannot fault: no source value forms an address.
+ * channels 1 forwards to vip_upsample_run_f32 (the same kernels, the same checks), so a caller
+ * generic over the channel count needs no branch. channels 2, 3 and 4 take every scale and every
+ * ksize the handle can have (odd, 1..9): there is no channel-dependent cap.
+ * Pitches are in bytes. The float bases and pitches must be multiples of 4; 16-byte accesses are
+ * used only where base and pitch are multiples of 16, decided separately for d_src_lo and d_dst.
+ * The guides may have any base and pitch. No byte of d_dst is written at a byte offset
+ * >= width * channels * 4 within a row, nor at a row >= height.
+ * VIP_ERR_INVALID_ARGUMENT: a null handle or pointer; channels outside 1..4; guide_channels not 1
+ * or 3; a misaligned float base or pitch; a pitch smaller than a row. VIP_ERR_ALIASING: d_dst
+ * equals any input. One launch per call (vip::upsample_f32c_kernel<R, S, C, GUIDE, FMA>),
+ * asynchronous, no device allocation; the launch log and vip_kernel_timing_* see it. Against C
+ * launches of vip_upsample_run_f32 on de-interleaved planes: see DESIGN.md section 4; nothing
+ * here promises a speed. */
+int vip_upsample_run_f32c(vip_upsample_t h, const float* d_src_lo, size_t src_pitch, int channels,
+                          const uint8_t* d_guide_lo, size_t guide_lo_pitch, const uint8_t* d_guide,
+                          size_t guide_pitch, int guide_channels, float* d_dst, size_t dst_pitch, void* stream);
 /* Tuning knob, process-wide (no reference counterpart): waves per workgroup of the plain
  * bilateral kernel for radius <= 8. 0 (default) = chosen per launch from the frame's
  * tile count (small frames take 8 or 4 waves and smaller tiles so more CUs work);

@@ -98,6 +98,9 @@ SIGNATURES = {
     "vip_upsample_run_f32": (
         _c_int, [_c_void_p, _c_void_p, _c_size_t, _c_void_p, _c_size_t, _c_void_p, _c_size_t, _c_int,
                  _c_void_p, _c_size_t, _c_void_p]),
+    "vip_upsample_run_f32c": (
+        _c_int, [_c_void_p, _c_void_p, _c_size_t, _c_int, _c_void_p, _c_size_t, _c_void_p, _c_size_t, _c_int,
+                 _c_void_p, _c_size_t, _c_void_p]),
     "vip_adaptive_create": (_c_int, [ctypes.POINTER(_c_void_p), _c_int, _c_int, _c_int, _c_float, _c_float, _c_int]),
     "vip_adaptive_destroy": (_c_int, [_c_void_p]),
     "vip_adaptive_run": (_c_int, [_c_void_p, _c_void_p, _c_size_t, _c_void_p, _c_size_t, _c_void_p]),

@@ -809,19 +809,22 @@ int vip_upsample_create(vip_upsample_t* out, int width, int height, int scale, i
     return 0;
 }
 
-int vip_upsample_run_f32(vip_upsample_t h, const float* d_src_lo, size_t src_pitch, const uint8_t* d_guide_lo,
-                         size_t guide_lo_pitch, const uint8_t* d_guide, size_t guide_pitch, int guide_channels,
-                         float* d_dst, size_t dst_pitch, void* stream) {
+// The checks and the kernel arguments of the two upsample entry points: a low-resolution cell and
+// an output pixel are `channels` floats; the 16-byte accesses are decided for src and dst each on
+// its own
+static int upsample_args(vip_upsample_t h, const float* d_src_lo, size_t src_pitch, int channels,
+                         const uint8_t* d_guide_lo, size_t guide_lo_pitch, const uint8_t* d_guide, size_t guide_pitch,
+                         int guide_channels, float* d_dst, size_t dst_pitch, UpsampleArgs& a) {
     if (!h || !d_src_lo || !d_guide_lo || !d_guide || !d_dst) return VIP_ERR_INVALID_ARGUMENT;
     if (guide_channels != 1 && guide_channels != 3) return VIP_ERR_INVALID_ARGUMENT;
     if (!is_aligned(d_src_lo, src_pitch, 4) || !is_aligned(d_dst, dst_pitch, 4)) return VIP_ERR_INVALID_ARGUMENT;
-    const size_t gch = (size_t)guide_channels;
-    if (src_pitch < sizeof(float) * h->low_width || guide_lo_pitch < gch * h->low_width ||
-        guide_pitch < gch * h->width || dst_pitch < sizeof(float) * h->width)
+    const size_t gch = (size_t)guide_channels, cell = sizeof(float) * (size_t)channels;
+    if (src_pitch < cell * h->low_width || guide_lo_pitch < gch * h->low_width || guide_pitch < gch * h->width ||
+        dst_pitch < cell * h->width)
         return VIP_ERR_INVALID_ARGUMENT;
     const void* const dst = d_dst;
     if (dst == d_src_lo || dst == d_guide_lo || dst == d_guide) return VIP_ERR_ALIASING;
-    UpsampleArgs a{};
+    a = UpsampleArgs{};
     a.src = reinterpret_cast<const uint8_t*>(d_src_lo);
     a.guide_lo = d_guide_lo;
     a.guide = d_guide;
@@ -840,8 +843,34 @@ int vip_upsample_run_f32(vip_upsample_t h, const float* d_src_lo, size_t src_pit
     a.dst_aligned = is_aligned(d_dst, dst_pitch, 16);
     a.color = h->d_color;
     a.wsp = h->d_wsp;
+    return 0;
+}
+
+int vip_upsample_run_f32(vip_upsample_t h, const float* d_src_lo, size_t src_pitch, const uint8_t* d_guide_lo,
+                         size_t guide_lo_pitch, const uint8_t* d_guide, size_t guide_pitch, int guide_channels,
+                         float* d_dst, size_t dst_pitch, void* stream) {
+    UpsampleArgs a;
+    if (const int rc = upsample_args(h, d_src_lo, src_pitch, 1, d_guide_lo, guide_lo_pitch, d_guide, guide_pitch,
+                                     guide_channels, d_dst, dst_pitch, a))
+        return rc;
     return launch_upsample_f32(h->radius, h->scale, guide_channels, h->numerics == VIP_NUMERICS_CUDA, a,
                                (hipStream_t)stream);
+}
+
+// ---- upsampling of an interleaved field of 2..4 channels (vip_upsample_f32c.hpp), on the same handle
+int vip_upsample_run_f32c(vip_upsample_t h, const float* d_src_lo, size_t src_pitch, int channels,
+                          const uint8_t* d_guide_lo, size_t guide_lo_pitch, const uint8_t* d_guide,
+                          size_t guide_pitch, int guide_channels, float* d_dst, size_t dst_pitch, void* stream) {
+    if (channels < 1 || channels > 4) return VIP_ERR_INVALID_ARGUMENT;
+    if (channels == 1)
+        return vip_upsample_run_f32(h, d_src_lo, src_pitch, d_guide_lo, guide_lo_pitch, d_guide, guide_pitch,
+                                    guide_channels, d_dst, dst_pitch, stream);
+    UpsampleArgs a;
+    if (const int rc = upsample_args(h, d_src_lo, src_pitch, channels, d_guide_lo, guide_lo_pitch, d_guide,
+                                     guide_pitch, guide_channels, d_dst, dst_pitch, a))
+        return rc;
+    return launch_upsample_f32c(h->radius, h->scale, channels, guide_channels, h->numerics == VIP_NUMERICS_CUDA, a,
+                                (hipStream_t)stream);
 }
 
 // The frames of a *_run_rows_batch call, or a run of them

@@ -218,6 +218,24 @@ void CudaJointBilateralUpsample::upsample_f32(const float* const d_src_lo, const
     VIP_REPORT(vip_device_synchronize());
 }
 
+void CudaJointBilateralUpsample::upsample_f32c(const float* const d_src_lo, const int channels,
+                                               const std::uint8_t* const d_guide_lo,
+                                               const std::uint8_t* const d_guide, const int guide_channels,
+                                               float* const d_dst, void* stream) const {
+    const size_t gch = guide_channels == 3 ? 3 : 1;
+    const size_t cell = sizeof(float) * (size_t)(channels > 0 ? channels : 1);  // the C ABI refuses channels < 1
+    VIP_REPORT(vip_upsample_run_f32c(handle_, d_src_lo, (size_t)low_width_ * cell, channels, d_guide_lo,
+                                     (size_t)low_width_ * gch, d_guide, (size_t)width_ * gch, guide_channels, d_dst,
+                                     (size_t)width_ * cell, stream));
+}
+void CudaJointBilateralUpsample::upsample_f32c(const float* const d_src_lo, const int channels,
+                                               const std::uint8_t* const d_guide_lo,
+                                               const std::uint8_t* const d_guide, const int guide_channels,
+                                               float* const d_dst) const {
+    upsample_f32c(d_src_lo, channels, d_guide_lo, d_guide, guide_channels, d_dst, nullptr);
+    VIP_REPORT(vip_device_synchronize());
+}
+
 // ------------------------------------------------------------ CudaAdaptiveBilateralFilter
 CudaAdaptiveBilateralFilter::Impl::Impl(const int width, const int height, const int ksize, const float sigma_space,
                                         const float sigma_color)

@@ -132,6 +132,26 @@ struct UpsampleArgs {
                                   // (2 ax + 1, 2 ay + 1) half pixels at [ay][ax]
 };
 int launch_upsample_f32(int radius, int scale, int guide_channels, bool fma, const UpsampleArgs& a, hipStream_t s);
+// vip_upsample_f32c.hpp: launch_upsample_f32's filter on an interleaved field of channels = 2..4, every
+// radius and scale. UpsampleArgs exactly as launch_upsample_f32 reads it: a cell of src and a pixel
+// of dst are C floats. One translation unit per channel count (vip_upsample_f32c_c2.hip, _c3, _c4)
+// instantiates the template.
+template <int C>
+int launch_upsample_f32c_channels(int radius, int scale, int guide_channels, bool fma, const UpsampleArgs& a,
+                                  hipStream_t s);
+// each unit compiles its own channel count only, also where it sees the template's definition
+extern template int launch_upsample_f32c_channels<2>(int, int, int, bool, const UpsampleArgs&, hipStream_t);
+extern template int launch_upsample_f32c_channels<3>(int, int, int, bool, const UpsampleArgs&, hipStream_t);
+extern template int launch_upsample_f32c_channels<4>(int, int, int, bool, const UpsampleArgs&, hipStream_t);
+inline int launch_upsample_f32c(int radius, int scale, int channels, int guide_channels, bool fma,
+                                const UpsampleArgs& a, hipStream_t s) {
+    switch (channels) {
+        case 2: return launch_upsample_f32c_channels<2>(radius, scale, guide_channels, fma, a, s);
+        case 3: return launch_upsample_f32c_channels<3>(radius, scale, guide_channels, fma, a, s);
+        case 4: return launch_upsample_f32c_channels<4>(radius, scale, guide_channels, fma, a, s);
+        default: return VIP_ERR_INVALID_ARGUMENT;
+    }
+}
 // vip_joint_conf.hip: the confidence-weighted form of launch_joint_f32 (radius 0..15, no
 // runtime-radius kernel). StencilArgs as launch_joint_f32 reads it (one whole frame), plus the
 // confidence plane, the optional weight output and the value written where no weight was in reach;

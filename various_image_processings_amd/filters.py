@@ -21,7 +21,9 @@ yuyuyu-bot/various_image_processings:
 * ``CudaJointBilateralUpsample(width, height, scale, ksize=5, sigma_space=1., sigma_color=30.)`` with
   ``upsample_f32(d_src_lo, d_guide_lo, d_guide, guide_channels, d_dst)``, ``low_width()`` and
   ``low_height()``: a float32 field at 1/2, 1/4 or 1/8 scale brought up to the frame under the
-  full-resolution 8-bit guide (no reference counterpart)
+  full-resolution 8-bit guide (no reference counterpart), and its multi-channel form
+  ``upsample_f32c(d_src_lo, channels, d_guide_lo, d_guide, guide_channels, d_dst)`` on an interleaved
+  field of 1..4 channels
 * ``cuda_gradient(d_src, d_dst, width, height, src_ch=1)`` (gradient.hpp:13-23)
 * ``DeviceImage(width, height, channels=1, dtype)`` with upload/download/get (device_image.hpp:4-16)
 
@@ -372,6 +374,19 @@ class _UpsampleImpl(_Handle):
              _ptr(d_guide_lo, lw * lh * gch), lw * gch, _ptr(d_guide, w * h * gch), w * gch, gch,
              _ptr(d_dst, 4 * w * h, dtype="float32"), 4 * w, _stream(stream))
 
+    def upsample_f32c(self, d_src_lo, channels, d_guide_lo, d_guide, guide_channels, d_dst, stream=None):
+        """upsample_f32 on an interleaved field of 1..4 channels (include/vip.h vip_upsample_run_f32c):
+        d_src_lo is low_width * low_height * channels float32 and d_dst width * height * channels,
+        every channel brought up under the same guides in one launch."""
+        gch = _BilateralImpl._guide_channels(guide_channels, "vip_upsample_run_f32c")
+        ch = int(channels)
+        if not 1 <= ch <= 4:
+            raise VipError("vip_upsample_run_f32c", _lib.VIP_ERR_INVALID_ARGUMENT)
+        (lw, lh), w, h = self._low, self.width, self.height
+        call("vip_upsample_run_f32c", self._h, _ptr(d_src_lo, 4 * lw * lh * ch, dtype="float32"), 4 * lw * ch, ch,
+             _ptr(d_guide_lo, lw * lh * gch), lw * gch, _ptr(d_guide, w * h * gch), w * gch, gch,
+             _ptr(d_dst, 4 * w * h * ch, dtype="float32"), 4 * w * ch, _stream(stream))
+
 
 class CudaJointBilateralUpsample:
     """include/cuda/joint_bilateral_upsample.hpp; the public call blocks until done. scale 2, 4 or
@@ -388,6 +403,11 @@ class CudaJointBilateralUpsample:
 
     def upsample_f32(self, d_src_lo, d_guide_lo, d_guide, guide_channels, d_dst):
         self.impl_.upsample_f32(d_src_lo, d_guide_lo, d_guide, guide_channels, d_dst)
+        device_synchronize()
+
+    def upsample_f32c(self, d_src_lo, channels, d_guide_lo, d_guide, guide_channels, d_dst):
+        """upsample_f32 on an interleaved field of 1..4 channels (include/vip.h vip_upsample_run_f32c)."""
+        self.impl_.upsample_f32c(d_src_lo, channels, d_guide_lo, d_guide, guide_channels, d_dst)
         device_synchronize()
 
 
