@@ -214,7 +214,8 @@ int vip_bilateral_run_rows_c1(vip_bilateral_t h, const uint8_t* d_src, size_t sr
  * every address comes from the guide. Sums that overflow give +-Inf, as in the definition.
  * Tie to the 8-bit form: for f == (float)g with a gray u8 frame g, u8(dst + 0.5f) is
  * vip_joint_bilateral_run_c1 on g, bit for bit (s and sumk are the same floats).
- * ksize 1..47 odd (VIP_ERR_UNSUPPORTED_KSIZE on a larger handle); ksize 1 copies f.
+ * ksize 1..47 odd (VIP_ERR_UNSUPPORTED_KSIZE on a larger handle); ksize 1 returns f, except that
+ * -0 becomes +0 (s starts at +0: fmaf(-0, 1, +0) = +0 and (+0) + (-0 * 1) = +0, in both profiles).
  * Pitches are in bytes. d_src and d_dst bases and pitches must be multiples of 4
  * (VIP_ERR_INVALID_ARGUMENT otherwise); any such value works: the kernels take 16-byte loads
  * and stores only where base and pitch are multiples of 16, dword accesses otherwise. d_guide

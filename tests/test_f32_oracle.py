@@ -94,6 +94,13 @@ def test_ksize_1_copies_the_source():
     guide = rng.integers(0, 256, (9, 13, 3), dtype=np.uint8)
     for profile in PROFILES:
         assert np.array_equal(_bits(f32_oracle.joint_bilateral(f, guide, 1, profile=profile)), _bits(f))
+    # ... except that -0 becomes +0 (include/vip.h): s starts at +0, and fmaf(-0, 1, +0) = +0
+    f[2, 3], f[4, 5] = np.float32(-0.0), np.float32(0.0)
+    assert _bits(f)[2, 3] == 0x80000000
+    for profile in PROFILES:
+        out = f32_oracle.joint_bilateral(f, guide, 1, profile=profile)
+        assert _bits(out)[2, 3] == 0 and _bits(out)[4, 5] == 0
+        assert np.array_equal(_bits(out), _bits(np.where(f == 0, np.float32(0.0), f)))
 
 
 # ---- 4. the entry points exist in every layer ----
