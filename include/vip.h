@@ -320,6 +320,68 @@ int vip_joint_bilateral_run_conf_f32(vip_bilateral_t h, const float* d_src, size
 int vip_joint_bilateral_run_f32c(vip_bilateral_t h, const float* d_src, size_t src_pitch, int channels,
                                  const uint8_t* d_guide, size_t guide_pitch, int guide_channels, float* d_dst,
                                  size_t dst_pitch, void* stream);
+/* ---- self-guided bilateral filter of an f32 one-channel image (no counterpart in the reference's
+ * API; OpenCV's cv::bilateralFilter takes CV_32F): a depth or disparity map on its own, an HDR
+ * luminance plane, a height field, the base layer of a tone-mapper. The float image is its own
+ * guide. As OpenCV's 32F path, the range weight is a quantised table with linear interpolation:
+ * N = VIP_BILATERAL_F32_BINS bins cover differences 0..value_range, so every operation is a
+ * binary32 operation and the range weight costs one table read per tap, not an exp.
+ * Tables, built on the host at create time; cf = -1.f / (2 * sigma_color * sigma_color) (float) and
+ * cd = -1. / (double)(2 * sigma_color * sigma_color), as the colour LUT of vip_bilateral_create:
+ *   scale    = (float)N / value_range                float division
+ *   v        = (float)i / scale                      float division, i = 0..N
+ *   L[i]     = expf((v * v) * cf)                    VIP_NUMERICS_CUDA: float product, host expf
+ *   L[i]     = (float)exp((double)v * (double)v * cd)   VIP_NUMERICS_CPP
+ *   L[N + 1] = L[N]
+ *   D[i]     = L[i + 1] - L[i]                       float, i = 0..N; D[N] = 0
+ *   ws       the spatial table of vip_bilateral_create at radius ksize / 2, exactly 0 outside the disc
+ * Per output pixel the taps run in row-major order over the k x k square, replicate border:
+ *   d    = |f_n - f_c|                  binary32 subtract, then abs
+ *   t    = min(d * scale, (float)N)
+ *   i    = (int)t;  a = t - (float)i    (exact)
+ *   wc   = fmaf(a, D[i], L[i])          VIP_NUMERICS_CUDA
+ *   wc   = L[i] + a * D[i]              VIP_NUMERICS_CPP (two roundings)
+ *   w    = ws[ky,kx] * wc
+ *   s    = fmaf(f_n, w, s)              VIP_NUMERICS_CUDA
+ *   s    = s + f_n * w                  VIP_NUMERICS_CPP
+ *   sumk = sumk + w
+ *   dst  = s / sumk                     IEEE binary32 division, no clamp
+ * Arithmetic is binary32 with gradual underflow (the kernels run in denormal mode 3, like their
+ * siblings). sumk >= 1 always: the centre tap has t = 0 and wc = L[0] = 1.
+ * Differences at or beyond value_range take the weight at value_range (t clamps to N): pass the
+ * image's max - min for OpenCV's behaviour; a smaller value_range clamps, it does not fail.
+ * Domain: every source value must be finite; the result then equals the definition bit for bit,
+ * in both profiles (a difference that overflows to +Inf clamps like any other). With an Inf or NaN
+ * in the source the values are unspecified, but the table index the kernel forms lies in [0, N]
+ * for every bit pattern of the source (the tap's v_min_f32 returns N for a NaN), so such a call
+ * reads nothing outside the table and cannot fault.
+ * Tie to the 8-bit form: with value_range = 1024 (bin width exactly 1) and f == (float)g for a
+ * gray u8 frame g, a is 0 at every tap, L[i] is the colour LUT's entry i bit for bit, and
+ * u8(dst + 0.5f) is vip_bilateral_run_c1 on g.
+ * ksize: odd, 1..vip_bilateral_f32_max_ksize() = 31 (VIP_ERR_UNSUPPORTED_KSIZE otherwise; the cap
+ * has its own function, vip_max_ksize knows no id for this filter). ksize 1 returns f, except that
+ * -0 becomes +0. Pitches are in bytes; d_src and d_dst bases and pitches must be multiples of 4,
+ * and any such value works: 16-byte accesses where base and pitch are multiples of 16, dwords
+ * otherwise. No byte of d_dst at column >= width or row >= out_rows is written.
+ * VIP_ERR_INVALID_ARGUMENT: null handle or pointer, non-positive size, a bad band, a misaligned
+ * base or pitch, a value_range that is not finite, not > 0, or gives a scale that is not finite
+ * and > 0 (the sigmas are taken as vip_bilateral_create takes them); VIP_ERR_ALIASING: d_dst equals
+ * d_src. One launch per call (vip::bilateral_f32_kernel<R, FMA>, R = ksize / 2), asynchronous, no
+ * device allocation at run time; there is no runtime-radius kernel and vip_set_stencil_path does
+ * not apply; the launch log and vip_kernel_timing_* see the kernel. The handle is read-only after
+ * create. The _rows form takes a row band as vip_joint_bilateral_run_rows_f32. Measured times:
+ * DESIGN.md section 4; nothing here promises a speed. */
+#define VIP_BILATERAL_F32_BINS 1024
+typedef struct vip_bilateral_f32_s* vip_bilateral_f32_t;
+int vip_bilateral_f32_max_ksize(void);
+int vip_bilateral_f32_create(vip_bilateral_f32_t* out, int width, int height, int ksize, float sigma_space,
+                             float sigma_color, float value_range, int numerics);
+int vip_bilateral_f32_destroy(vip_bilateral_f32_t h);
+int vip_bilateral_f32_run(vip_bilateral_f32_t h, const float* d_src, size_t src_pitch, float* d_dst,
+                          size_t dst_pitch, void* stream);
+int vip_bilateral_f32_run_rows(vip_bilateral_f32_t h, const float* d_src, size_t src_pitch, float* d_dst,
+                               size_t dst_pitch, int out_rows, int src_row0, int row_lo, int row_hi,
+                               void* stream);
 /* ---- joint bilateral upsampling (Kopf et al. 2007; no counterpart in the reference's API): a
  * field f solved at 1/2, 1/4 or 1/8 scale is brought up to the frame under the full-resolution
  * image, in one launch, with no full-resolution float intermediate.

@@ -24,9 +24,11 @@ from .filters import (  # noqa: F401
     VIP_NUMERICS_CUDA,
     CudaAdaptiveBilateralFilter,
     CudaBilateralFilter,
+    CudaBilateralFilterF32,
     CudaBilateralTextureFilter,
     CudaJointBilateralUpsample,
     DeviceImage,
+    _BilateralF32Impl,
     cuda_gradient,
     device_synchronize,
     kernel_timing,

@@ -1,0 +1,11 @@
+// Self-guided f32 bilateral (vip_bilateral_f32.hpp): the kernels of radius 15, fused multiply-add (CUDA profile).
+#include "vip_bilateral_f32.hpp"
+
+namespace vip {
+
+template <>
+int launch_bilateral_f32_part<true, 3>(int radius, const BilateralF32Args& a, hipStream_t s) {
+    return launch_bf32_part<true, 3>(radius, a, s);
+}
+
+}  // namespace vip

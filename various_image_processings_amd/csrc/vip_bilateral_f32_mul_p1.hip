@@ -1,0 +1,11 @@
+// Self-guided f32 bilateral (vip_bilateral_f32.hpp): the kernels of radii 12 and 13, separate multiply and add (CPP profile).
+#include "vip_bilateral_f32.hpp"
+
+namespace vip {
+
+template <>
+int launch_bilateral_f32_part<false, 1>(int radius, const BilateralF32Args& a, hipStream_t s) {
+    return launch_bf32_part<false, 1>(radius, a, s);
+}
+
+}  // namespace vip

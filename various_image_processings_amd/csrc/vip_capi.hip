@@ -101,6 +101,8 @@ constexpr int kMaxKsizeJointConf = 2 * kMaxRadius + 1;
 // the multi-channel f32 joint filter likewise (C + 1 LDS planes): by channel count, index 0 unused;
 // one channel is the f32 joint filter itself
 constexpr int kMaxKsizeJointF32c[5] = {0, kMaxKsizeJoint, 31, 15, 15};
+// the self-guided f32 bilateral has the radius-specialised kernels only (vip_bilateral_f32_max_ksize)
+constexpr int kMaxKsizeBilateralF32 = 2 * kMaxRadius + 1;
 static bool valid_ksize(int ksize, int max_ksize) { return ksize >= 1 && (ksize & 1) && ksize <= max_ksize; }
 
 // vip_set_stencil_path: VIP_PATH_AUTO (templated kernels for radius 1..15, the
@@ -529,7 +531,7 @@ const char* vip_error_string(int code) {
         case VIP_ERR_INVALID_ARGUMENT: return "invalid argument";
         case VIP_ERR_UNSUPPORTED_KSIZE:
             return "unsupported ksize (odd, 1..65 bilateral, 1..47 joint bilateral, 1..63 adaptive, 1..9 upsampling, 1..31 confidence-weighted "
-                   "joint, 1..31 / 1..15 joint on 2 / 3-4 f32 channels; texture 1..24)";
+                   "joint, 1..31 / 1..15 joint on 2 / 3-4 f32 channels, 1..31 self-guided f32 bilateral; texture 1..24)";
         case VIP_ERR_ALIASING: return "source and destination alias";
         default: return hipGetErrorString((hipError_t)code);
     }
@@ -747,6 +749,86 @@ int vip_joint_bilateral_run_f32c(vip_bilateral_t h, const float* d_src, size_t s
     a.dst_aligned = is_aligned(d_dst, dst_pitch, 16);
     const bool fma = h->numerics == VIP_NUMERICS_CUDA;
     return launch_joint_f32c(h->radius, channels, guide_channels, fma, a, (hipStream_t)stream);
+}
+
+// ---- self-guided f32 bilateral (vip_bilateral_f32.hpp): a handle of its own, since the range
+// table depends on value_range. The StencilHandle part carries the geometry, the spatial table
+// and, as d_color, the device table of kBf32Pairs (L[i], D[i]) pairs; it has no runtime-radius tables.
+struct vip_bilateral_f32_s : StencilHandle {
+    float scale;
+};
+
+int vip_bilateral_f32_max_ksize(void) { return kMaxKsizeBilateralF32; }
+
+int vip_bilateral_f32_create(vip_bilateral_f32_t* out, int width, int height, int ksize, float sigma_space,
+                             float sigma_color, float value_range, int numerics) {
+    constexpr int N = VIP_BILATERAL_F32_BINS;
+    if (!out || width <= 0 || height <= 0) return VIP_ERR_INVALID_ARGUMENT;
+    if (!std::isfinite(value_range) || !(value_range > 0.f)) return VIP_ERR_INVALID_ARGUMENT;
+    const float scale = (float)N / value_range;
+    if (!std::isfinite(scale) || !(scale > 0.f)) return VIP_ERR_INVALID_ARGUMENT;
+    if (!valid_ksize(ksize, kMaxKsizeBilateralF32)) return VIP_ERR_UNSUPPORTED_KSIZE;
+    vip_bilateral_f32_s* h = new (std::nothrow) vip_bilateral_f32_s();
+    if (!h) return (int)hipErrorOutOfMemory;
+    h->width = width;
+    h->height = height;
+    h->ksize = ksize;
+    h->radius = ksize / 2;
+    h->numerics = numerics == VIP_NUMERICS_CPP ? VIP_NUMERICS_CPP : VIP_NUMERICS_CUDA;
+    h->lut_nonzero = 0;
+    h->scale = scale;
+    build_space_q(h->radius, sigma_space, h->numerics, h->wsq);
+    // the range table: L at the differences i / scale (build_color's coefficients), its slopes beside it
+    const float two_s2 = 2 * sigma_color * sigma_color;
+    const float cf = -1.f / two_s2;
+    const double cd = -1. / (double)two_s2;
+    std::vector<float> L(N + 2), pairs(2 * (size_t)kBf32Pairs);
+    for (int i = 0; i <= N; ++i) {
+        const float v = (float)i / scale;
+        L[i] = h->numerics == VIP_NUMERICS_CPP ? (float)std::exp((double)v * (double)v * cd) : expf((v * v) * cf);
+    }
+    L[N + 1] = L[N];
+    for (int i = 0; i <= N; ++i) {
+        pairs[2 * i] = L[i];
+        pairs[2 * i + 1] = L[i + 1] - L[i];
+    }
+    int rc = (int)hipMalloc(reinterpret_cast<void**>(&h->d_color), sizeof(float) * pairs.size());
+    if (!rc) rc = (int)hipMemcpy(h->d_color, pairs.data(), sizeof(float) * pairs.size(), hipMemcpyHostToDevice);
+    if (rc) {
+        vip_bilateral_f32_destroy(h);
+        return rc;
+    }
+    *out = h;
+    return 0;
+}
+
+int vip_bilateral_f32_destroy(vip_bilateral_f32_t h) {
+    if (!h) return 0;
+    const int rc = h->d_color ? (int)hipFree(h->d_color) : 0;
+    delete h;
+    return rc;
+}
+
+int vip_bilateral_f32_run_rows(vip_bilateral_f32_t h, const float* d_src, size_t src_pitch, float* d_dst,
+                               size_t dst_pitch, int out_rows, int src_row0, int row_lo, int row_hi,
+                               void* stream) {
+    if (!h) return VIP_ERR_INVALID_ARGUMENT;
+    const RowBand b{reinterpret_cast<const uint8_t*>(d_src), src_pitch, nullptr, 0,
+                    reinterpret_cast<uint8_t*>(d_dst), dst_pitch, out_rows, src_row0, row_lo, row_hi};
+    if (const int rc = check_band(h->height, b)) return rc;
+    if (!is_aligned(d_src, src_pitch, 4) || !is_aligned(d_dst, dst_pitch, 4)) return VIP_ERR_INVALID_ARGUMENT;
+    BilateralF32Args a;
+    static_cast<StencilArgs&>(a) = stencil_args(*h, b);
+    a.aligned = is_aligned(d_src, src_pitch, 16) ? kF32SrcVec : 0;
+    a.dst_aligned = is_aligned(d_dst, dst_pitch, 16);
+    a.scale = h->scale;
+    return launch_bilateral_f32(h->radius, h->numerics == VIP_NUMERICS_CUDA, a, (hipStream_t)stream);
+}
+
+int vip_bilateral_f32_run(vip_bilateral_f32_t h, const float* d_src, size_t src_pitch, float* d_dst,
+                          size_t dst_pitch, void* stream) {
+    if (!h) return VIP_ERR_INVALID_ARGUMENT;
+    return vip_bilateral_f32_run_rows(h, d_src, src_pitch, d_dst, dst_pitch, h->height, 0, 0, h->height, stream);
 }
 
 // ---- joint bilateral upsampling (vip_upsample.hip): a handle of its own, since the spatial

@@ -9,6 +9,7 @@
 #include <stdexcept>
 #include <string>
 
+#include "cuda/bilateral_filter_f32.hpp"
 #include "cuda/device_image.hpp"
 #include "cuda/gradient.hpp"
 #include "cuda/joint_bilateral_upsample.hpp"
@@ -233,6 +234,35 @@ void CudaJointBilateralUpsample::upsample_f32c(const float* const d_src_lo, cons
                                                const std::uint8_t* const d_guide, const int guide_channels,
                                                float* const d_dst) const {
     upsample_f32c(d_src_lo, channels, d_guide_lo, d_guide, guide_channels, d_dst, nullptr);
+    VIP_REPORT(vip_device_synchronize());
+}
+
+// ------------------------------------------------------------ CudaBilateralFilterF32
+CudaBilateralFilterF32::Impl::Impl(const int width, const int height, const int ksize, const float sigma_space,
+                                   const float sigma_color, const float value_range)
+    : width_(width) {
+    const int rc = vip_bilateral_f32_create(&handle_, width, height, ksize, sigma_space, sigma_color, value_range,
+                                            VIP_NUMERICS_CUDA);
+    if (rc) fail("CudaBilateralFilterF32", rc);
+}
+CudaBilateralFilterF32::Impl::~Impl() { vip_bilateral_f32_destroy(handle_); }
+
+void CudaBilateralFilterF32::Impl::bilateral_filter(const float* const d_src, float* const d_dst, void* stream) const {
+    const size_t pitch = (size_t)width_ * sizeof(float);
+    VIP_REPORT(vip_bilateral_f32_run(handle_, d_src, pitch, d_dst, pitch, stream));
+}
+
+CudaBilateralFilterF32::CudaBilateralFilterF32(const int width, const int height, const int ksize,
+                                               const float sigma_space, const float sigma_color,
+                                               const float value_range)
+    : impl_(std::make_unique<Impl>(width, height, ksize, sigma_space, sigma_color, value_range)) {}
+CudaBilateralFilterF32::~CudaBilateralFilterF32() = default;
+
+void CudaBilateralFilterF32::bilateral_filter(const float* const d_src, float* const d_dst, void* stream) const {
+    impl_->bilateral_filter(d_src, d_dst, stream);
+}
+void CudaBilateralFilterF32::bilateral_filter(const float* const d_src, float* const d_dst) const {
+    impl_->bilateral_filter(d_src, d_dst, nullptr);
     VIP_REPORT(vip_device_synchronize());
 }
 

@@ -169,6 +169,41 @@ int launch_joint_conf_f32(int radius, int guide_channels, bool fma, const ConfAr
 // (radius 0..15 at C = 2, 0..7 at C = 3 and 4, VIP_ERR_UNSUPPORTED_KSIZE beyond; no runtime-radius
 // kernel). StencilArgs exactly as launch_joint_f32 reads it: a pixel of src and dst is C floats.
 int launch_joint_f32c(int radius, int channels, int guide_channels, bool fma, const StencilArgs& a, hipStream_t s);
+// vip_bilateral_f32.hpp: the self-guided f32 bilateral filter (radius 0..15, no runtime-radius
+// kernel). StencilArgs as launch_joint_f32 reads it, without a guide (guide == src, never read as
+// one): src and dst carry the float pointers, `aligned` holds kF32SrcVec, dst_aligned means 16-byte
+// aligned, and color points at the handle's range table: kBf32Pairs (L[i], D[i]) float pairs,
+// i = 0..VIP_BILATERAL_F32_BINS. The struct is this kernel's alone.
+constexpr int kBf32Pairs = VIP_BILATERAL_F32_BINS + 1;
+struct BilateralF32Args : StencilArgs {
+    float scale;  // (float)VIP_BILATERAL_F32_BINS / value_range
+};
+// vip_bilateral_f32.hpp is instantiated by one unit per arithmetic and radius group (part),
+// vip_bilateral_f32_fma_p0.hip .. _mul_p3.hip: each defines one specialization of
+// launch_bilateral_f32_part, for the radii kBf32PartLo[part]..kBf32PartHi[part].
+constexpr int kBf32Parts = 4;
+constexpr int kBf32PartLo[kBf32Parts] = {0, 12, 14, 15};
+constexpr int kBf32PartHi[kBf32Parts] = {11, 13, 14, 15};
+static_assert(kBf32PartHi[kBf32Parts - 1] == kMaxRadius, "the parts cover radius 0..kMaxRadius");
+template <bool FMA, int PART>
+int launch_bilateral_f32_part(int radius, const BilateralF32Args& a, hipStream_t s);
+#define VIP_BF32_DECLARE_PART(FMA, PART) \
+    template <>                          \
+    int launch_bilateral_f32_part<FMA, PART>(int radius, const BilateralF32Args& a, hipStream_t s);
+VIP_BF32_DECLARE_PART(true, 0) VIP_BF32_DECLARE_PART(true, 1) VIP_BF32_DECLARE_PART(true, 2) VIP_BF32_DECLARE_PART(true, 3)
+VIP_BF32_DECLARE_PART(false, 0) VIP_BF32_DECLARE_PART(false, 1) VIP_BF32_DECLARE_PART(false, 2) VIP_BF32_DECLARE_PART(false, 3)
+#undef VIP_BF32_DECLARE_PART
+template <bool FMA>
+inline int launch_bilateral_f32_fma(int radius, const BilateralF32Args& a, hipStream_t s) {
+    if (radius < 0 || radius > kMaxRadius) return VIP_ERR_UNSUPPORTED_KSIZE;
+    if (radius <= kBf32PartHi[0]) return launch_bilateral_f32_part<FMA, 0>(radius, a, s);
+    if (radius <= kBf32PartHi[1]) return launch_bilateral_f32_part<FMA, 1>(radius, a, s);
+    if (radius <= kBf32PartHi[2]) return launch_bilateral_f32_part<FMA, 2>(radius, a, s);
+    return launch_bilateral_f32_part<FMA, 3>(radius, a, s);
+}
+inline int launch_bilateral_f32(int radius, bool fma, const BilateralF32Args& a, hipStream_t s) {
+    return fma ? launch_bilateral_f32_fma<true>(radius, a, s) : launch_bilateral_f32_fma<false>(radius, a, s);
+}
 int launch_gradient_u8(const uint8_t* src, float* dst, int width, int height, int ch, hipStream_t stream);
 int launch_gradient_f32(const float* src, float* dst, int width, int height, int ch, bool fma, hipStream_t stream);
 int launch_blur_rtv(const uint8_t* img, const float* mag, float* blurred, float* rtv, int width, int height,

@@ -43,7 +43,7 @@ from ._lib import VIP_NUMERICS_CPP, VIP_NUMERICS_CUDA, VipError, call, lib
 
 __all__ = [
     "CudaBilateralFilter", "CudaAdaptiveBilateralFilter", "CudaBilateralTextureFilter", "cuda_gradient",
-    "CudaJointBilateralUpsample",
+    "CudaJointBilateralUpsample", "CudaBilateralFilterF32", "_BilateralF32Impl",
     "DeviceImage", "VipError", "VIP_NUMERICS_CUDA", "VIP_NUMERICS_CPP", "device_synchronize",
     "set_bilateral_waves", "set_bilateral_wide", "set_bilateral_frames_in_flight", "launched_kernels", "kernel_timing", "set_stencil_path", "max_ksize",
 ]
@@ -408,6 +408,46 @@ class CudaJointBilateralUpsample:
     def upsample_f32c(self, d_src_lo, channels, d_guide_lo, d_guide, guide_channels, d_dst):
         """upsample_f32 on an interleaved field of 1..4 channels (include/vip.h vip_upsample_run_f32c)."""
         self.impl_.upsample_f32c(d_src_lo, channels, d_guide_lo, d_guide, guide_channels, d_dst)
+        device_synchronize()
+
+
+class _BilateralF32Impl(_Handle):
+    """Self-guided bilateral filter of an f32 one-channel image (include/vip.h vip_bilateral_f32_*;
+    no reference counterpart): no synchronisation. value_range: the span of differences the
+    1024-bin range table covers; larger differences take the weight at value_range."""
+    _destroy = "vip_bilateral_f32_destroy"
+
+    def __init__(self, width, height, ksize=9, sigma_space=10.0, sigma_color=30.0, value_range=255.0,
+                 numerics=VIP_NUMERICS_CUDA):
+        super().__init__()
+        self.width, self.height, self.ksize = int(width), int(height), int(ksize)
+        call("vip_bilateral_f32_create", ctypes.byref(self._h), self.width, self.height, self.ksize,
+             float(sigma_space), float(sigma_color), float(value_range), int(numerics))
+
+    def bilateral_filter(self, d_src, d_dst, stream=None):
+        """d_src, d_dst: width x height float32, dense."""
+        p, n = 4 * self.width, 4 * self.width * self.height
+        call("vip_bilateral_f32_run", self._h, _ptr(d_src, n, dtype="float32"), p, _ptr(d_dst, n, dtype="float32"), p,
+             _stream(stream))
+
+    def run_rows(self, d_src, d_dst, out_rows, src_row0, row_lo, row_hi, stream=None):
+        """Row band (include/vip.h vip_bilateral_f32_run_rows): d_src holds rows [0, row_hi) at
+        least, d_dst out_rows rows."""
+        p = 4 * self.width
+        call("vip_bilateral_f32_run_rows", self._h, _ptr(d_src, p * int(row_hi), dtype="float32"), p,
+             _ptr(d_dst, p * int(out_rows), dtype="float32"), p, int(out_rows), int(src_row0), int(row_lo),
+             int(row_hi), _stream(stream))
+
+
+class CudaBilateralFilterF32:
+    """include/cuda/bilateral_filter_f32.hpp; the public call blocks until done. ksize odd, 1..31."""
+
+    def __init__(self, width, height, ksize=9, sigma_space=10.0, sigma_color=30.0, value_range=255.0,
+                 numerics=VIP_NUMERICS_CUDA):
+        self.impl_ = _BilateralF32Impl(width, height, ksize, sigma_space, sigma_color, value_range, numerics)
+
+    def bilateral_filter(self, d_src, d_dst):
+        self.impl_.bilateral_filter(d_src, d_dst)
         device_synchronize()
 
 
