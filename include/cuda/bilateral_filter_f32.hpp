@@ -3,7 +3,10 @@
 // (vip_bilateral_f32_*, libvip_hip.so, gfx950 HIP kernels), which holds the definition.
 // Pointers are device pointers to dense width x height float images. value_range is the span of
 // differences the 1024-bin range table covers (pass the image's max - min; larger differences take
-// the weight at value_range). ksize odd, 1..31. The public call blocks until the GPU is done, like
+// the weight at value_range). ksize odd, 1..31. The forms with `channels` (1..3) take dense images of
+// that many interleaved floats per pixel; the range weight then comes from the L1 distance over the
+// channels, value_range is the largest such distance the table covers (channels * (max - min) for
+// OpenCV's behaviour), and ksize stops at 15 for 2 and 3 channels. The public call blocks until the GPU is done, like
 // the other classes' public calls; the Impl's call (and the public one with a stream, a hipStream_t
 // passed as void*, nullptr = default stream) enqueues and returns at once.
 #ifndef VIP_CUDA_BILATERAL_FILTER_F32_HPP
@@ -21,6 +24,8 @@ public:
 
     void bilateral_filter(const float* const d_src, float* const d_dst) const;
     void bilateral_filter(const float* const d_src, float* const d_dst, void* stream) const;
+    void bilateral_filter(const float* const d_src, const int channels, float* const d_dst) const;
+    void bilateral_filter(const float* const d_src, const int channels, float* const d_dst, void* stream) const;
 
     // no synchronisation
     class Impl {
@@ -31,6 +36,8 @@ public:
         Impl(const Impl&) = delete;
         Impl& operator=(const Impl&) = delete;
         void bilateral_filter(const float* const d_src, float* const d_dst, void* stream = nullptr) const;
+        void bilateral_filter(const float* const d_src, const int channels, float* const d_dst,
+                              void* stream = nullptr) const;
 
     private:
         const int width_;

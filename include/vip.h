@@ -382,6 +382,56 @@ int vip_bilateral_f32_run(vip_bilateral_f32_t h, const float* d_src, size_t src_
 int vip_bilateral_f32_run_rows(vip_bilateral_f32_t h, const float* d_src, size_t src_pitch, float* d_dst,
                                size_t dst_pitch, int out_rows, int src_row0, int row_lo, int row_hi,
                                void* stream);
+/* ---- self-guided bilateral filter of an f32 image of 2 or 3 interleaved channels: linear-light or
+ * HDR RGB, a Lab frame, a normal map, a 2-channel flow field. The other half of OpenCV's CV_32F
+ * bilateral (CV_32FC3): one range weight per tap, from the L1 distance over the channels, as the
+ * 8-bit colour filter forms it. The handle is a vip_bilateral_f32_t as it stands: its tables scale,
+ * L, D and ws are used exactly as above, and create knows nothing of the channel count.
+ * The source is f_c(p), c = 0..C-1, C floats per pixel. Per output pixel the taps run in row-major
+ * order over the k x k square, replicate border:
+ *   d    = |f_0(n) - f_0(c)| + |f_1(n) - f_1(c)|                          C = 2
+ *   d    = (|f_0(n) - f_0(c)| + |f_1(n) - f_1(c)|) + |f_2(n) - f_2(c)|    C = 3
+ *           binary32 subtract, abs, then binary32 adds left to right
+ *   t    = min(d * scale, (float)N);  i = (int)t;  a = t - (float)i
+ *   wc   = fmaf(a, D[i], L[i])            VIP_NUMERICS_CUDA
+ *   wc   = L[i] + a * D[i]                VIP_NUMERICS_CPP
+ *   w    = ws[ky,kx] * wc                 formed once per tap
+ *   s_c  = fmaf(f_c(n), w, s_c)  or  s_c + f_c(n) * w    for each channel
+ *   sumk = sumk + w                       once per tap
+ *   dst_c = s_c / sumk                    IEEE binary32 division
+ * value_range is therefore the largest L1 distance that the N bins cover: a caller who wants
+ * OpenCV's behaviour passes C * (max - min); a smaller value clamps (t = N), it does not fail.
+ * Domain: as the one-channel filter's. Finite input gives the definition bit for bit in both
+ * profiles; a sum of differences that overflows to +Inf clamps to N like any other. With a NaN or
+ * Inf in the source the values are unspecified, but the table index lies in [0, N] for every bit
+ * pattern: d * scale is the result of a multiply, and the tap's v_min_f32 returns N for a NaN.
+ * Three identities follow. With value_range = 1024 and f == (float)g for a u8 3-channel frame g,
+ * d <= 765, a is 0 at every tap and u8(dst_c + 0.5f) is vip_bilateral_run on g. If every channel
+ * but channel 0 is constant over the frame, channel 0 of the result is vip_bilateral_f32_run on
+ * plane 0 bit for bit (the other terms of d are exactly +0). ksize 1 returns f with -0 turned
+ * into +0, per channel.
+ * channels: 1, 2 or 3; anything else is VIP_ERR_INVALID_ARGUMENT. channels == 1 forwards to
+ * vip_bilateral_f32_run / _run_rows (same kernels, same checks), so a caller generic over the
+ * channel count needs no branch. Four channels are deliberately not offered: whether alpha takes
+ * part in the distance has no agreed answer (filter the colour here and alpha on its own, or use
+ * vip_joint_bilateral_run_f32c under a guide).
+ * ksize: vip_bilateral_f32_max_ksize_c(channels) is 31 for 1 channel, 15 for 2 and 3, and 0 for any
+ * other count; a handle whose ksize is above the cap for the given channel count gives
+ * VIP_ERR_UNSUPPORTED_KSIZE at run. Every other rule is the one-channel filter's: pitches are in
+ * bytes and at least width * channels * 4 (VIP_ERR_INVALID_ARGUMENT otherwise); d_src and d_dst
+ * bases and pitches must be multiples of 4; 16-byte accesses are used only where base and pitch are
+ * multiples of 16, decided separately for source and destination; no byte of d_dst is written at a
+ * byte offset >= width * channels * 4 within a row, nor at a row >= out_rows; VIP_ERR_ALIASING when
+ * d_dst equals d_src. One launch per call (vip::bilateral_f32c_kernel<R, C, FMA>, R = ksize / 2 in
+ * 1..7; vip::bilateral_f32c_k1_kernel<C, FMA> for ksize 1), asynchronous, no device allocation; the
+ * launch log and vip_kernel_timing_* see the kernel. The _rows form takes the band of
+ * vip_bilateral_f32_run_rows. Measured times: DESIGN.md section 4; nothing here promises a speed. */
+int vip_bilateral_f32_max_ksize_c(int channels);
+int vip_bilateral_f32_run_c(vip_bilateral_f32_t h, const float* d_src, size_t src_pitch, int channels,
+                            float* d_dst, size_t dst_pitch, void* stream);
+int vip_bilateral_f32_run_rows_c(vip_bilateral_f32_t h, const float* d_src, size_t src_pitch, int channels,
+                                 float* d_dst, size_t dst_pitch, int out_rows, int src_row0, int row_lo,
+                                 int row_hi, void* stream);
 /* ---- joint bilateral upsampling (Kopf et al. 2007; no counterpart in the reference's API): a
  * field f solved at 1/2, 1/4 or 1/8 scale is brought up to the frame under the full-resolution
  * image, in one launch, with no full-resolution float intermediate.

@@ -831,6 +831,45 @@ int vip_bilateral_f32_run(vip_bilateral_f32_t h, const float* d_src, size_t src_
     return vip_bilateral_f32_run_rows(h, d_src, src_pitch, d_dst, dst_pitch, h->height, 0, 0, h->height, stream);
 }
 
+// ---- the self-guided f32 bilateral on an interleaved image of 2 or 3 channels (vip_bilateral_f32c.hpp):
+// the same handle, tables and band; a row is width * channels floats, the 16-byte accesses are
+// decided for src and dst each on its own, and channels == 1 is the one-channel entry point itself
+constexpr int kMaxKsizeBilateralF32c[4] = {0, kMaxKsizeBilateralF32, 2 * kBf32cMaxRadius + 1, 2 * kBf32cMaxRadius + 1};
+
+int vip_bilateral_f32_max_ksize_c(int channels) {
+    return channels >= 1 && channels <= 3 ? kMaxKsizeBilateralF32c[channels] : 0;
+}
+
+int vip_bilateral_f32_run_rows_c(vip_bilateral_f32_t h, const float* d_src, size_t src_pitch, int channels,
+                                 float* d_dst, size_t dst_pitch, int out_rows, int src_row0, int row_lo, int row_hi,
+                                 void* stream) {
+    if (channels < 1 || channels > 3) return VIP_ERR_INVALID_ARGUMENT;
+    if (channels == 1)
+        return vip_bilateral_f32_run_rows(h, d_src, src_pitch, d_dst, dst_pitch, out_rows, src_row0, row_lo, row_hi,
+                                          stream);
+    if (!h) return VIP_ERR_INVALID_ARGUMENT;
+    const RowBand b{reinterpret_cast<const uint8_t*>(d_src), src_pitch, nullptr, 0,
+                    reinterpret_cast<uint8_t*>(d_dst), dst_pitch, out_rows, src_row0, row_lo, row_hi};
+    if (const int rc = check_band(h->height, b)) return rc;
+    if (!is_aligned(d_src, src_pitch, 4) || !is_aligned(d_dst, dst_pitch, 4)) return VIP_ERR_INVALID_ARGUMENT;
+    const size_t frow = sizeof(float) * (size_t)channels * (size_t)h->width;
+    if (src_pitch < frow || dst_pitch < frow) return VIP_ERR_INVALID_ARGUMENT;
+    if (h->ksize > kMaxKsizeBilateralF32c[channels]) return VIP_ERR_UNSUPPORTED_KSIZE;
+    BilateralF32Args a;
+    static_cast<StencilArgs&>(a) = stencil_args(*h, b);
+    a.aligned = is_aligned(d_src, src_pitch, 16) ? kF32SrcVec : 0;
+    a.dst_aligned = is_aligned(d_dst, dst_pitch, 16);
+    a.scale = h->scale;
+    return launch_bilateral_f32c(h->radius, channels, h->numerics == VIP_NUMERICS_CUDA, a, (hipStream_t)stream);
+}
+
+int vip_bilateral_f32_run_c(vip_bilateral_f32_t h, const float* d_src, size_t src_pitch, int channels, float* d_dst,
+                            size_t dst_pitch, void* stream) {
+    if (!h) return VIP_ERR_INVALID_ARGUMENT;
+    return vip_bilateral_f32_run_rows_c(h, d_src, src_pitch, channels, d_dst, dst_pitch, h->height, 0, 0, h->height,
+                                        stream);
+}
+
 // ---- joint bilateral upsampling (vip_upsample.hip): a handle of its own, since the spatial
 // table depends on the scale
 static bool valid_scale(int s) { return s == 2 || s == 4 || s == 8; }

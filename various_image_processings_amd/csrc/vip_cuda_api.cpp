@@ -251,6 +251,11 @@ void CudaBilateralFilterF32::Impl::bilateral_filter(const float* const d_src, fl
     const size_t pitch = (size_t)width_ * sizeof(float);
     VIP_REPORT(vip_bilateral_f32_run(handle_, d_src, pitch, d_dst, pitch, stream));
 }
+void CudaBilateralFilterF32::Impl::bilateral_filter(const float* const d_src, const int channels, float* const d_dst,
+                                                    void* stream) const {
+    const size_t pitch = (size_t)width_ * sizeof(float) * (size_t)(channels > 0 ? channels : 1);  // the C ABI refuses channels < 1
+    VIP_REPORT(vip_bilateral_f32_run_c(handle_, d_src, pitch, channels, d_dst, pitch, stream));
+}
 
 CudaBilateralFilterF32::CudaBilateralFilterF32(const int width, const int height, const int ksize,
                                                const float sigma_space, const float sigma_color,
@@ -263,6 +268,14 @@ void CudaBilateralFilterF32::bilateral_filter(const float* const d_src, float* c
 }
 void CudaBilateralFilterF32::bilateral_filter(const float* const d_src, float* const d_dst) const {
     impl_->bilateral_filter(d_src, d_dst, nullptr);
+    VIP_REPORT(vip_device_synchronize());
+}
+void CudaBilateralFilterF32::bilateral_filter(const float* const d_src, const int channels, float* const d_dst,
+                                              void* stream) const {
+    impl_->bilateral_filter(d_src, channels, d_dst, stream);
+}
+void CudaBilateralFilterF32::bilateral_filter(const float* const d_src, const int channels, float* const d_dst) const {
+    impl_->bilateral_filter(d_src, channels, d_dst, nullptr);
     VIP_REPORT(vip_device_synchronize());
 }
 

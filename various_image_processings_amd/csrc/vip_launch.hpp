@@ -204,6 +204,27 @@ inline int launch_bilateral_f32_fma(int radius, const BilateralF32Args& a, hipSt
 inline int launch_bilateral_f32(int radius, bool fma, const BilateralF32Args& a, hipStream_t s) {
     return fma ? launch_bilateral_f32_fma<true>(radius, a, s) : launch_bilateral_f32_fma<false>(radius, a, s);
 }
+// vip_bilateral_f32c.hpp: launch_bilateral_f32's filter on an interleaved f32 image of channels = 2 or 3,
+// the range weight from the L1 distance over the channels (radius 0..kBf32cMaxRadius,
+// VIP_ERR_UNSUPPORTED_KSIZE beyond; no runtime-radius kernel). BilateralF32Args exactly as
+// launch_bilateral_f32 reads it: a pixel of src and dst is C floats. One translation unit per channel
+// count and arithmetic (vip_bilateral_f32c_c2_fma.hip .. _c3_mul.hip) instantiates the template.
+constexpr int kBf32cMaxRadius = 7;
+template <int C, bool FMA>
+int launch_bilateral_f32c_unit(int radius, const BilateralF32Args& a, hipStream_t s);
+// each unit compiles its own pair only, also where it sees the template's definition
+extern template int launch_bilateral_f32c_unit<2, true>(int, const BilateralF32Args&, hipStream_t);
+extern template int launch_bilateral_f32c_unit<2, false>(int, const BilateralF32Args&, hipStream_t);
+extern template int launch_bilateral_f32c_unit<3, true>(int, const BilateralF32Args&, hipStream_t);
+extern template int launch_bilateral_f32c_unit<3, false>(int, const BilateralF32Args&, hipStream_t);
+inline int launch_bilateral_f32c(int radius, int channels, bool fma, const BilateralF32Args& a, hipStream_t s) {
+    if (radius < 0 || radius > kBf32cMaxRadius) return VIP_ERR_UNSUPPORTED_KSIZE;
+    switch (channels) {
+        case 2: return fma ? launch_bilateral_f32c_unit<2, true>(radius, a, s) : launch_bilateral_f32c_unit<2, false>(radius, a, s);
+        case 3: return fma ? launch_bilateral_f32c_unit<3, true>(radius, a, s) : launch_bilateral_f32c_unit<3, false>(radius, a, s);
+        default: return VIP_ERR_INVALID_ARGUMENT;
+    }
+}
 int launch_gradient_u8(const uint8_t* src, float* dst, int width, int height, int ch, hipStream_t stream);
 int launch_gradient_f32(const float* src, float* dst, int width, int height, int ch, bool fma, hipStream_t stream);
 int launch_blur_rtv(const uint8_t* img, const float* mag, float* blurred, float* rtv, int width, int height,

@@ -438,9 +438,33 @@ class _BilateralF32Impl(_Handle):
              _ptr(d_dst, p * int(out_rows), dtype="float32"), p, int(out_rows), int(src_row0), int(row_lo),
              int(row_hi), _stream(stream))
 
+    @staticmethod
+    def _channels(channels, fn):
+        """The buffer sizes depend on it, so a count the C ABI refuses is refused here, with its code."""
+        ch = int(channels)
+        if not 1 <= ch <= 3:
+            raise VipError(fn, _lib.VIP_ERR_INVALID_ARGUMENT)
+        return ch
+
+    def bilateral_filter_c(self, d_src, channels, d_dst, stream=None):
+        """d_src, d_dst: width x height pixels of `channels` (1..3) interleaved float32, dense; the range
+        weight comes from the L1 distance over the channels (include/vip.h vip_bilateral_f32_run_c)."""
+        c = self._channels(channels, "vip_bilateral_f32_run_c")
+        p, n = 4 * c * self.width, 4 * c * self.width * self.height
+        call("vip_bilateral_f32_run_c", self._h, _ptr(d_src, n, dtype="float32"), p, int(channels),
+             _ptr(d_dst, n, dtype="float32"), p, _stream(stream))
+
+    def run_rows_c(self, d_src, channels, d_dst, out_rows, src_row0, row_lo, row_hi, stream=None):
+        """run_rows on `channels` interleaved channels (include/vip.h vip_bilateral_f32_run_rows_c)."""
+        p = 4 * self._channels(channels, "vip_bilateral_f32_run_rows_c") * self.width
+        call("vip_bilateral_f32_run_rows_c", self._h, _ptr(d_src, p * int(row_hi), dtype="float32"), p, int(channels),
+             _ptr(d_dst, p * int(out_rows), dtype="float32"), p, int(out_rows), int(src_row0), int(row_lo),
+             int(row_hi), _stream(stream))
+
 
 class CudaBilateralFilterF32:
-    """include/cuda/bilateral_filter_f32.hpp; the public call blocks until done. ksize odd, 1..31."""
+    """include/cuda/bilateral_filter_f32.hpp; the public call blocks until done. ksize odd, 1..31
+    (1..15 for the 2- and 3-channel form)."""
 
     def __init__(self, width, height, ksize=9, sigma_space=10.0, sigma_color=30.0, value_range=255.0,
                  numerics=VIP_NUMERICS_CUDA):
@@ -448,6 +472,11 @@ class CudaBilateralFilterF32:
 
     def bilateral_filter(self, d_src, d_dst):
         self.impl_.bilateral_filter(d_src, d_dst)
+        device_synchronize()
+
+    def bilateral_filter_c(self, d_src, channels, d_dst):
+        """bilateral_filter on an interleaved image of 1..3 channels (include/vip.h vip_bilateral_f32_run_c)."""
+        self.impl_.bilateral_filter_c(d_src, channels, d_dst)
         device_synchronize()
 
 
