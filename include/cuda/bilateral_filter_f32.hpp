@@ -26,6 +26,12 @@ public:
     void bilateral_filter(const float* const d_src, float* const d_dst, void* stream) const;
     void bilateral_filter(const float* const d_src, const int channels, float* const d_dst) const;
     void bilateral_filter(const float* const d_src, const int channels, float* const d_dst, void* stream) const;
+    // the range weight from a second one-channel float image of the same size, the guide
+    // (vip_bilateral_f32_run_joint: a depth map under a luminance plane); value_range is then the
+    // span of guide differences; d_guide == d_src gives bilateral_filter's result
+    void joint_bilateral_filter(const float* const d_src, const float* const d_guide, float* const d_dst) const;
+    void joint_bilateral_filter(const float* const d_src, const float* const d_guide, float* const d_dst,
+                                void* stream) const;
 
     // no synchronisation
     class Impl {
@@ -38,6 +44,8 @@ public:
         void bilateral_filter(const float* const d_src, float* const d_dst, void* stream = nullptr) const;
         void bilateral_filter(const float* const d_src, const int channels, float* const d_dst,
                               void* stream = nullptr) const;
+        void joint_bilateral_filter(const float* const d_src, const float* const d_guide, float* const d_dst,
+                                    void* stream = nullptr) const;
 
     private:
         const int width_;

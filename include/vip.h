@@ -432,6 +432,54 @@ int vip_bilateral_f32_run_c(vip_bilateral_f32_t h, const float* d_src, size_t sr
 int vip_bilateral_f32_run_rows_c(vip_bilateral_f32_t h, const float* d_src, size_t src_pitch, int channels,
                                  float* d_dst, size_t dst_pitch, int out_rows, int src_row0, int row_lo,
                                  int row_hi, void* stream);
+/* ---- joint bilateral filter of an f32 one-channel source f under an f32 one-channel guide g of the
+ * same size (no counterpart in the reference's API; OpenCV's ximgproc::jointBilateralFilter takes
+ * CV_32F guides): a noisy depth or disparity map under an HDR or linear-light luminance plane, a
+ * flow component or a matte under a depth map, a path-traced radiance plane under its depth
+ * buffer. The handle is a vip_bilateral_f32_t as vip_bilateral_f32_create makes it: the same
+ * scale, L, D and ws, N = VIP_BILATERAL_F32_BINS. value_range is the span of guide differences
+ * the bins cover. Per output pixel the taps run in row-major order over the k x k square, with a
+ * replicate border on both images:
+ *   d    = |g_n - g_c|                  binary32 subtract, then abs
+ *   t    = min(d * scale, (float)N)
+ *   i    = (int)t;  a = t - (float)i    (exact)
+ *   wc   = fmaf(a, D[i], L[i])          VIP_NUMERICS_CUDA
+ *   wc   = L[i] + a * D[i]              VIP_NUMERICS_CPP (two roundings)
+ *   w    = ws[ky,kx] * wc
+ *   s    = fmaf(f_n, w, s)              VIP_NUMERICS_CUDA
+ *   s    = s + f_n * w                  VIP_NUMERICS_CPP
+ *   sumk = sumk + w
+ *   dst  = s / sumk                     IEEE binary32 division, no clamp
+ * Arithmetic is binary32 with gradual underflow; sumk >= 1 always (the centre tap has wc = L[0] = 1).
+ * Domain: f and g must be finite; the result then equals the definition bit for bit, in both
+ * profiles. With an Inf or NaN anywhere the values are unspecified, but the table index the kernel
+ * forms lies in [0, N] for every bit pattern of the guide (d * scale is a product, and the tap's
+ * v_min_f32 returns N for a NaN), and no address is formed from the source, so such a call reads
+ * nothing outside the table and cannot fault.
+ * Ties: with g == f the result is vip_bilateral_f32_run's bit for bit. With value_range = 1024 (bin
+ * width exactly 1) and g == (float)g8 for a gray u8 frame g8, a is 0 at every tap, L[i] is the
+ * colour LUT's entry i, and the result is vip_joint_bilateral_run_f32 under g8 (guide_channels 1)
+ * bit for bit at the same sigmas.
+ * ksize: odd, 1..vip_bilateral_f32_max_ksize_joint() = 31; a handle whose ksize is above the cap
+ * gives VIP_ERR_UNSUPPORTED_KSIZE at run. ksize 1 returns f, except that -0 becomes +0, and does
+ * not read the guide. Pitches are in bytes and at least width * 4; bases and pitches of d_src,
+ * d_guide and d_dst must be multiples of 4, and any such value works: 16-byte accesses are used
+ * only where a buffer's base and pitch are multiples of 16, decided for source, guide and
+ * destination each on its own. No byte of d_dst at column >= width or row >= out_rows is written.
+ * The _rows form takes a row band as vip_bilateral_f32_run_rows; rows of both images clamp into
+ * [row_lo, row_hi). VIP_ERR_INVALID_ARGUMENT: null handle or pointer (a null guide too), a bad
+ * band, a misaligned base or pitch, a pitch below width * 4; VIP_ERR_ALIASING: d_dst equals d_src
+ * or d_guide. d_guide == d_src is allowed: it gives the self-guided result and still launches this
+ * filter's kernel. One launch per call (vip::bilateral_f32_joint_kernel<R, FMA>, R = ksize / 2),
+ * asynchronous, no device allocation; the launch log and vip_kernel_timing_* see the kernel.
+ * Measured times: DESIGN.md section 4; nothing here promises a speed. */
+int vip_bilateral_f32_max_ksize_joint(void);
+int vip_bilateral_f32_run_joint(vip_bilateral_f32_t h, const float* d_src, size_t src_pitch,
+                                const float* d_guide, size_t guide_pitch, float* d_dst, size_t dst_pitch,
+                                void* stream);
+int vip_bilateral_f32_run_rows_joint(vip_bilateral_f32_t h, const float* d_src, size_t src_pitch,
+                                     const float* d_guide, size_t guide_pitch, float* d_dst, size_t dst_pitch,
+                                     int out_rows, int src_row0, int row_lo, int row_hi, void* stream);
 /* ---- joint bilateral upsampling (Kopf et al. 2007; no counterpart in the reference's API): a
  * field f solved at 1/2, 1/4 or 1/8 scale is brought up to the frame under the full-resolution
  * image, in one launch, with no full-resolution float intermediate.

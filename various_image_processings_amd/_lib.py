@@ -104,6 +104,12 @@ SIGNATURES = {
     "vip_bilateral_f32_run_rows_c": (
         _c_int, [_c_void_p, _c_void_p, _c_size_t, _c_int, _c_void_p, _c_size_t, _c_int, _c_int, _c_int, _c_int,
                  _c_void_p]),
+    "vip_bilateral_f32_max_ksize_joint": (_c_int, []),
+    "vip_bilateral_f32_run_joint": (
+        _c_int, [_c_void_p, _c_void_p, _c_size_t, _c_void_p, _c_size_t, _c_void_p, _c_size_t, _c_void_p]),
+    "vip_bilateral_f32_run_rows_joint": (
+        _c_int, [_c_void_p, _c_void_p, _c_size_t, _c_void_p, _c_size_t, _c_void_p, _c_size_t, _c_int, _c_int, _c_int,
+                 _c_int, _c_void_p]),
     "vip_upsample_create": (
         _c_int, [ctypes.POINTER(_c_void_p), _c_int, _c_int, _c_int, _c_int, _c_float, _c_float, _c_int]),
     "vip_upsample_destroy": (_c_int, [_c_void_p]),

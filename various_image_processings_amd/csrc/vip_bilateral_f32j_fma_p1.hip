@@ -1,0 +1,11 @@
+// f32 joint bilateral under an f32 guide (vip_bilateral_f32j.hpp): the kernels of radii 12 and 13, fused multiply-add (CUDA profile).
+#include "vip_bilateral_f32j.hpp"
+
+namespace vip {
+
+template <>
+int launch_bilateral_f32_joint_part<true, 1>(int radius, const BilateralF32Args& a, hipStream_t s) {
+    return launch_bf32j_part<true, 1>(radius, a, s);
+}
+
+}  // namespace vip

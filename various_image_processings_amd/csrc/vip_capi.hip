@@ -870,6 +870,40 @@ int vip_bilateral_f32_run_c(vip_bilateral_f32_t h, const float* d_src, size_t sr
                                         stream);
 }
 
+// ---- the f32 bilateral under a second f32 one-channel image, the guide (vip_bilateral_f32j.hpp):
+// the same handle, tables and band; the 16-byte accesses are decided for src, guide and dst each on
+// its own. d_guide == d_src gives the self-guided result through this filter's own kernel.
+constexpr int kMaxKsizeBilateralF32Joint = 2 * kMaxRadius + 1;
+
+int vip_bilateral_f32_max_ksize_joint(void) { return kMaxKsizeBilateralF32Joint; }
+
+int vip_bilateral_f32_run_rows_joint(vip_bilateral_f32_t h, const float* d_src, size_t src_pitch,
+                                     const float* d_guide, size_t guide_pitch, float* d_dst, size_t dst_pitch,
+                                     int out_rows, int src_row0, int row_lo, int row_hi, void* stream) {
+    if (!h || !d_guide) return VIP_ERR_INVALID_ARGUMENT;
+    const RowBand b{reinterpret_cast<const uint8_t*>(d_src), src_pitch, reinterpret_cast<const uint8_t*>(d_guide),
+                    guide_pitch, reinterpret_cast<uint8_t*>(d_dst), dst_pitch, out_rows, src_row0, row_lo, row_hi};
+    if (const int rc = check_band(h->height, b)) return rc;
+    if (!is_aligned(d_src, src_pitch, 4) || !is_aligned(d_guide, guide_pitch, 4) || !is_aligned(d_dst, dst_pitch, 4))
+        return VIP_ERR_INVALID_ARGUMENT;
+    const size_t frow = sizeof(float) * (size_t)h->width;
+    if (src_pitch < frow || guide_pitch < frow || dst_pitch < frow) return VIP_ERR_INVALID_ARGUMENT;
+    if (h->ksize > kMaxKsizeBilateralF32Joint) return VIP_ERR_UNSUPPORTED_KSIZE;
+    BilateralF32Args a;
+    static_cast<StencilArgs&>(a) = stencil_args(*h, b);
+    a.aligned = (is_aligned(d_src, src_pitch, 16) ? kF32SrcVec : 0) | (is_aligned(d_guide, guide_pitch, 16) ? kF32GuideVec : 0);
+    a.dst_aligned = is_aligned(d_dst, dst_pitch, 16);
+    a.scale = h->scale;
+    return launch_bilateral_f32_joint(h->radius, h->numerics == VIP_NUMERICS_CUDA, a, (hipStream_t)stream);
+}
+
+int vip_bilateral_f32_run_joint(vip_bilateral_f32_t h, const float* d_src, size_t src_pitch, const float* d_guide,
+                                size_t guide_pitch, float* d_dst, size_t dst_pitch, void* stream) {
+    if (!h) return VIP_ERR_INVALID_ARGUMENT;
+    return vip_bilateral_f32_run_rows_joint(h, d_src, src_pitch, d_guide, guide_pitch, d_dst, dst_pitch, h->height, 0,
+                                            0, h->height, stream);
+}
+
 // ---- joint bilateral upsampling (vip_upsample.hip): a handle of its own, since the spatial
 // table depends on the scale
 static bool valid_scale(int s) { return s == 2 || s == 4 || s == 8; }

@@ -256,6 +256,11 @@ void CudaBilateralFilterF32::Impl::bilateral_filter(const float* const d_src, co
     const size_t pitch = (size_t)width_ * sizeof(float) * (size_t)(channels > 0 ? channels : 1);  // the C ABI refuses channels < 1
     VIP_REPORT(vip_bilateral_f32_run_c(handle_, d_src, pitch, channels, d_dst, pitch, stream));
 }
+void CudaBilateralFilterF32::Impl::joint_bilateral_filter(const float* const d_src, const float* const d_guide,
+                                                          float* const d_dst, void* stream) const {
+    const size_t pitch = (size_t)width_ * sizeof(float);
+    VIP_REPORT(vip_bilateral_f32_run_joint(handle_, d_src, pitch, d_guide, pitch, d_dst, pitch, stream));
+}
 
 CudaBilateralFilterF32::CudaBilateralFilterF32(const int width, const int height, const int ksize,
                                                const float sigma_space, const float sigma_color,
@@ -276,6 +281,15 @@ void CudaBilateralFilterF32::bilateral_filter(const float* const d_src, const in
 }
 void CudaBilateralFilterF32::bilateral_filter(const float* const d_src, const int channels, float* const d_dst) const {
     impl_->bilateral_filter(d_src, channels, d_dst, nullptr);
+    VIP_REPORT(vip_device_synchronize());
+}
+void CudaBilateralFilterF32::joint_bilateral_filter(const float* const d_src, const float* const d_guide,
+                                                    float* const d_dst, void* stream) const {
+    impl_->joint_bilateral_filter(d_src, d_guide, d_dst, stream);
+}
+void CudaBilateralFilterF32::joint_bilateral_filter(const float* const d_src, const float* const d_guide,
+                                                    float* const d_dst) const {
+    impl_->joint_bilateral_filter(d_src, d_guide, d_dst, nullptr);
     VIP_REPORT(vip_device_synchronize());
 }
 

@@ -225,6 +225,39 @@ inline int launch_bilateral_f32c(int radius, int channels, bool fma, const Bilat
         default: return VIP_ERR_INVALID_ARGUMENT;
     }
 }
+// vip_bilateral_f32j.hpp: launch_bilateral_f32's filter with the distance taken from a second f32
+// one-channel image, the guide (radius 0..15, no runtime-radius kernel). BilateralF32Args as
+// launch_bilateral_f32 reads it, with guide and guide_pitch the float guide's (guide == src is
+// allowed and still read as a guide); `aligned` is a set of kF32SrcVec and kF32GuideVec. One unit
+// per arithmetic and radius group, vip_bilateral_f32j_fma_p0.hip .. _mul_p3.hip, as above.
+constexpr int kF32GuideVec = 8;  // float guide base and pitch are 16-byte aligned -> float4 loads
+constexpr int kBf32jParts = 4;
+constexpr int kBf32jPartLo[kBf32jParts] = {0, 12, 14, 15};
+constexpr int kBf32jPartHi[kBf32jParts] = {11, 13, 14, 15};
+static_assert(kBf32jPartHi[kBf32jParts - 1] == kMaxRadius, "the parts cover radius 0..kMaxRadius");
+template <bool FMA, int PART>
+int launch_bilateral_f32_joint_part(int radius, const BilateralF32Args& a, hipStream_t s);
+// each unit compiles its own specialization only
+template <> int launch_bilateral_f32_joint_part<true, 0>(int radius, const BilateralF32Args& a, hipStream_t s);
+template <> int launch_bilateral_f32_joint_part<true, 1>(int radius, const BilateralF32Args& a, hipStream_t s);
+template <> int launch_bilateral_f32_joint_part<true, 2>(int radius, const BilateralF32Args& a, hipStream_t s);
+template <> int launch_bilateral_f32_joint_part<true, 3>(int radius, const BilateralF32Args& a, hipStream_t s);
+template <> int launch_bilateral_f32_joint_part<false, 0>(int radius, const BilateralF32Args& a, hipStream_t s);
+template <> int launch_bilateral_f32_joint_part<false, 1>(int radius, const BilateralF32Args& a, hipStream_t s);
+template <> int launch_bilateral_f32_joint_part<false, 2>(int radius, const BilateralF32Args& a, hipStream_t s);
+template <> int launch_bilateral_f32_joint_part<false, 3>(int radius, const BilateralF32Args& a, hipStream_t s);
+template <bool FMA>
+inline int launch_bilateral_f32_joint_fma(int radius, const BilateralF32Args& a, hipStream_t s) {
+    if (radius < 0 || radius > kMaxRadius) return VIP_ERR_UNSUPPORTED_KSIZE;
+    if (radius <= kBf32jPartHi[0]) return launch_bilateral_f32_joint_part<FMA, 0>(radius, a, s);
+    if (radius <= kBf32jPartHi[1]) return launch_bilateral_f32_joint_part<FMA, 1>(radius, a, s);
+    if (radius <= kBf32jPartHi[2]) return launch_bilateral_f32_joint_part<FMA, 2>(radius, a, s);
+    return launch_bilateral_f32_joint_part<FMA, 3>(radius, a, s);
+}
+inline int launch_bilateral_f32_joint(int radius, bool fma, const BilateralF32Args& a, hipStream_t s) {
+    return fma ? launch_bilateral_f32_joint_fma<true>(radius, a, s)
+               : launch_bilateral_f32_joint_fma<false>(radius, a, s);
+}
 int launch_gradient_u8(const uint8_t* src, float* dst, int width, int height, int ch, hipStream_t stream);
 int launch_gradient_f32(const float* src, float* dst, int width, int height, int ch, bool fma, hipStream_t stream);
 int launch_blur_rtv(const uint8_t* img, const float* mag, float* blurred, float* rtv, int width, int height,

@@ -461,6 +461,21 @@ class _BilateralF32Impl(_Handle):
              _ptr(d_dst, p * int(out_rows), dtype="float32"), p, int(out_rows), int(src_row0), int(row_lo),
              int(row_hi), _stream(stream))
 
+    def joint_bilateral_filter(self, d_src, d_guide, d_dst, stream=None):
+        """d_src, d_guide, d_dst: width x height float32, dense; the range weight comes from the guide's
+        differences, which value_range spans (include/vip.h vip_bilateral_f32_run_joint)."""
+        p, n = 4 * self.width, 4 * self.width * self.height
+        call("vip_bilateral_f32_run_joint", self._h, _ptr(d_src, n, dtype="float32"), p,
+             _ptr(d_guide, n, dtype="float32"), p, _ptr(d_dst, n, dtype="float32"), p, _stream(stream))
+
+    def run_rows_joint(self, d_src, d_guide, d_dst, out_rows, src_row0, row_lo, row_hi, stream=None):
+        """run_rows under a float guide (include/vip.h vip_bilateral_f32_run_rows_joint): d_src and d_guide
+        hold rows [0, row_hi) at least, d_dst out_rows rows."""
+        p = 4 * self.width
+        call("vip_bilateral_f32_run_rows_joint", self._h, _ptr(d_src, p * int(row_hi), dtype="float32"), p,
+             _ptr(d_guide, p * int(row_hi), dtype="float32"), p, _ptr(d_dst, p * int(out_rows), dtype="float32"), p,
+             int(out_rows), int(src_row0), int(row_lo), int(row_hi), _stream(stream))
+
 
 class CudaBilateralFilterF32:
     """include/cuda/bilateral_filter_f32.hpp; the public call blocks until done. ksize odd, 1..31
@@ -477,6 +492,12 @@ class CudaBilateralFilterF32:
     def bilateral_filter_c(self, d_src, channels, d_dst):
         """bilateral_filter on an interleaved image of 1..3 channels (include/vip.h vip_bilateral_f32_run_c)."""
         self.impl_.bilateral_filter_c(d_src, channels, d_dst)
+        device_synchronize()
+
+    def joint_bilateral_filter(self, d_src, d_guide, d_dst):
+        """The one-channel filter with the range weight from a float guide image (include/vip.h
+        vip_bilateral_f32_run_joint)."""
+        self.impl_.joint_bilateral_filter(d_src, d_guide, d_dst)
         device_synchronize()
 
 
